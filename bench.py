@@ -17,6 +17,11 @@ value = instances that reached the KKT tolerance (status 0) on all ranks * K / m
 that end with another status (the random scenes include unavoidable collisions, i.e. locally infeasible NLPs) are
 counted in config.failed_per_step and are NOT part of value, though their time is.
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline does not need: the
+end-to-end rate through host pointers, the CPU baseline, for N > 1 the K steps once more without the all-gather and the check
+of the gathered block, for C5 the hold-on-failure re-run.  --dump-outputs DIR writes the arrays the last timed step returned
+(DIR/<name>.npy, float64; the inputs are seeded, so two builds can be compared output for output).
+
 PARITY STATUS: unpinned versus the reference's own solver (CasADi + IPOPT is not installed here or on the GPU box, the
 reference holds no golden outputs): solutions are checked against this repository's CPU oracle and an independent KKT
 certificate, see DESIGN.md §4.
@@ -187,6 +192,24 @@ def cpu_baseline_closed_loop(cfg, x0, xs, obs, sim_steps, min_seconds=8.0):
             "note": "own FP64 C++ restatement (oracle) driving the same loop; CasADi+IPOPT baseline unavailable (casadi not installed)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, integer ones converted to float64 (exact).  Should the whole exceed
+    DUMP_LIMIT_BYTES, each array keeps a fixed, seeded sample of its rows and the sorted row indices go to DIR/<name>_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= DUMP_LIMIT_BYTES else 0.3 * DUMP_LIMIT_BYTES / total     # row indices (8 bytes) cost at most twice a row
+    for name, a in arrays.items():
+        if frac < 1.0 and a.ndim and len(a) > 1:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 class Group:
     """The ranks of this run.  world = 1: nothing to do.  world > 1 (or MPCB_BENCH_FORCE_DIST=1, the one-rank rehearsal): a
     communication handle joins the RCCL group inside libmpcbatch (mpcb_comm_init_rank); the 128-byte group id travels from rank
@@ -209,7 +232,8 @@ class Group:
 
 
 def closed_loop_bench(args, bs, cfg, x0, xs, obs, workload, grp, local_rank):
-    """C5: `steps` // 10 (at least one) complete 80-step closed loops over all scenes; value counts solved MPC steps per second.
+    """C5: one step = one complete 80-step closed loop over all scenes (`warmup` untimed, then `steps` timed); value counts
+    solved MPC steps per second.
     The scenes are split over a few solver handles, each running its own closed loop from its own host thread (the steps of one
     loop depend on each other, independent loops overlap on the GPU like the launches of the other configurations)."""
     import threading
@@ -221,7 +245,6 @@ def closed_loop_bench(args, bs, cfg, x0, xs, obs, workload, grp, local_rank):
     parts = np.array_split(np.arange(len(x0)), F)
     for h_ in H:
         h_.closed_loop_sampled(_abi.SCENES_C3, 256, 1, steps=4, obs_motion=_abi.OBSMOVE_PREDICTED)
-        h_.timing(reset=True)
     res = [None] * F
 
     seed = 4000                                               # one Monte-Carlo population; rank r draws scenes [r*B, (r+1)*B) of it
@@ -241,9 +264,13 @@ def closed_loop_bench(args, bs, cfg, x0, xs, obs, workload, grp, local_rank):
             t_.join()
         return {k: np.concatenate([r_[k] for r_ in res]) for k in ("status", "iters", "x_hist", "u_hist", "x0", "obs0")}
 
+    for _ in range(args.warmup):
+        loops(False)
+    for h_ in H:
+        h_.timing(reset=True)
     grp.barrier()
     t0 = time.perf_counter()
-    reps = max(1, args.steps // 10)
+    reps = args.steps
     for _ in range(reps):
         out = loops(False)
     for h_ in H:
@@ -251,7 +278,9 @@ def closed_loop_bench(args, bs, cfg, x0, xs, obs, workload, grp, local_rank):
     grp.barrier()
     dt = time.perf_counter() - t0
     tms = [h_.timing() for h_ in H]
-    held = loops(True)                                        # the same scenes once more with the hold-and-shift fallback (untimed)
+    if args.dump_outputs and grp.rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    held = loops(True) if args.full else None                # the same scenes once more with the hold-and-shift fallback (untimed)
     status, iters = out["status"], out["iters"]
     x0, obs = out["x0"], out["obs0"]                          # the scenes the device drew
     xs = np.tile(x0[:1] * 0 + np.array([400.0, 3.5, 0.0, 30.0]), (len(x0), 1))
@@ -269,7 +298,11 @@ def closed_loop_bench(args, bs, cfg, x0, xs, obs, workload, grp, local_rank):
         return (float(h[ok].min()) if ok.any() else None), float(np.nanmin(h)), int(ok.sum()), int((np.nanmin(h, axis=(1, 2)) < -1e-6).sum())
 
     m_ok, m_all, n_ok, n_coll = min_margin(out)
-    mh_ok, mh_all, nh_ok, nh_coll = min_margin(held)
+    with_hold = None
+    if held is not None:
+        mh_ok, mh_all, nh_ok, nh_coll = min_margin(held)
+        with_hold = {"scenes_all_steps_solved": nh_ok, "min_h_scenes_all_solved": mh_ok, "min_h_all_scenes": mh_all,
+                     "scenes_with_collision": nh_coll, "failed_steps": int((held["status"] != 0).sum())}
     tot = grp.reduce([dt, 0.0], "max"); dt_max = float(tot[0])
     sums = grp.reduce([float(solved), float(B), float(n_ok)], "sum")
     nx, nz, ng = dims(cfg)
@@ -285,8 +318,7 @@ def closed_loop_bench(args, bs, cfg, x0, xs, obs, workload, grp, local_rank):
                    "failure_rate_steps": 1.0 - sums[0] / (sums[1] * sim_steps),
                    "status_histogram": {str(k): int(v) for k, v in enumerate(np.bincount(status.ravel(), minlength=7))},
                    "scenes_all_steps_solved": int(sums[2]), "min_h_scenes_all_solved": m_ok, "min_h_all_scenes": m_all, "scenes_with_collision": n_coll,
-                   "with_hold_on_failure": {"scenes_all_steps_solved": nh_ok, "min_h_scenes_all_solved": mh_ok, "min_h_all_scenes": mh_all,
-                                            "scenes_with_collision": nh_coll, "failed_steps": int((held["status"] != 0).sum())},
+                   "with_hold_on_failure": with_hold,
                    "iters_mean": float(iters.mean()), "iters_max": int(iters.max()), "scenes_drawn_on_device": True, "loops_in_flight": F,
                    "launches": launches, "restoration": bool(cfg.restoration), "collective": "none (scenes are independent for their whole horizon)",
                    "parity": PARITY_NOTE},
@@ -297,7 +329,7 @@ def closed_loop_bench(args, bs, cfg, x0, xs, obs, workload, grp, local_rank):
                      "note": "compulsory I/O only; the solve is LDS-resident, bound by FP64 VALU issue and the serial Riccati chain (DESIGN.md §5)"},
     }
     if grp.rank == 0:
-        if not args.no_cpu_baseline and grp.world == 1:
+        if args.full and not args.no_cpu_baseline and grp.world == 1:
             res_line["cpu_baseline"] = cpu_baseline_closed_loop(cfg, x0, xs, obs, sim_steps)
         print(json.dumps(res_line))
     return 0
@@ -306,13 +338,18 @@ def closed_loop_bench(args, bs, cfg, x0, xs, obs, workload, grp, local_rank):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (C5: timed closed loops); ms_per_step is the time of one")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed steps before them")
     ap.add_argument("--batch", type=int, default=None, help="instances per GPU per step (default: the config's BASELINE batch)")
     ap.add_argument("--config", default="C2", choices=["C2", "C3", "C4", "C5"],
                     help="BASELINE.json config: C2 (default, the metric's config) kin+1 static obstacle B=4096; C3 kin+3 predicted "
                          "obstacles B=32768; C4 dyn N=40 3 obstacles B=8192/GPU; C5 closed loop 80 steps (solves = scenes x steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: end_to_end (host-pointer entry), cpu_baseline, "
+                         "value_without_gather and the gathered-block check (N > 1), C5's hold-on-failure re-run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--no-restoration", action="store_true", help="cfg.restoration = 0: a failed line search ends the solve (round-1 behaviour)")
     ap.add_argument("--inflight", type=int, default=16,
                     help="launch lanes of the solver handle (mpcb_set_inflight): a batch is cut into that many chunks, chunk c of step k+1 "
@@ -335,6 +372,8 @@ def main():
                     help="C2/C3/C4 only: time the NEXT receding-horizon step, started from the shifted solution of a cold solve "
                          "(main_cbf_kin_c_sim.py:16-26,92) instead of the cold start z0=0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -427,7 +466,7 @@ def main():
     def step(gather=True):
         k = cyc[0]; cyc[0] += 1
         d = D[k % NB]; hq = k % HN; sl = (k // HN) % R; mark = hq * R + sl
-        o = OUT[hq][sl]; last[k % NB] = o; last["z"] = o["z"]
+        o = OUT[hq][sl]; last[k % NB] = o; last["z"] = o["z"]; last["o"] = o
         if grp.active and gather:
             H[hq].wait_mark(grp.h, mark)                # only the gather that last read THIS z buffer must be done (R steps ago), not the latest one
         H[hq].solve_device(B, d["x0"], d["xs"], d["obs"], obs_kind, d_z0, o["z"], o["obj"], o["st"], o["it"], o["kkt"])
@@ -457,7 +496,13 @@ def main():
         step()
     fence()
     dt = time.perf_counter() - t0
-    if grp.active:      # the gathered block of this rank must equal what its last solve wrote
+    if args.dump_outputs and rank == 0:     # what the last timed step returned, before anything can reuse its output set
+        o = last["o"]
+        arrays = dict(z=o["z"].download(), obj=o["obj"].download(), status=o["st"].download(), iters=o["it"].download(), kkt=o["kkt"].download())
+        if grp.active:
+            arrays["z_gathered"] = z_all.download()
+        dump_outputs(args.dump_outputs, arrays)
+    if grp.active and args.full:      # the gathered block of this rank must equal what its last solve wrote
         got = z_all.download()[rank * B:(rank + 1) * B]
         assert np.array_equal(got, last["z"].download()), "all-gather result differs from the solver output"
     tms = [h_.timing() for h_ in H]
@@ -479,7 +524,7 @@ def main():
     status = np.concatenate([s_ for u, s_ in zip(uses, st_b) if u]); iters = np.concatenate([i_ for u, i_ in zip(uses, it_b) if u])
     iters_per_launch = sum(u * float(i_.sum()) for u, i_ in zip(uses, it_b)) / max(1, args.steps)
     dt_nogather = None
-    if grp.active:      # the same K steps once more without the gather, reported next to the headline value
+    if grp.active and args.full:      # the same K steps once more without the gather, reported next to the headline value
         cyc[0] = 0
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -492,7 +537,7 @@ def main():
     # end to end through the host-pointer entry (mpcb_solve: pageable H2D of the inputs + solve + D2H of z, obj, status, iters, kkt),
     # the PCIe-inclusive rate; never `value`
     e2e = None
-    if rank == 0 and not args.warm:
+    if rank == 0 and not args.warm and args.full:
         bs.solve_batch(x0, xs, obs)
         t1 = time.perf_counter(); reps_e = 3; ok_e = 0
         for _ in range(reps_e):
@@ -555,7 +600,7 @@ def main():
                              "note": "compulsory I/O of the inputs actually passed (%s z0): x0, xs, obs in; z, obj, status, iters out" % ("with" if with_z0 else "no")},
             "end_to_end": e2e,
         }
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(cfg, x0, xs, obs)
         print(json.dumps(out))
     grp.barrier()

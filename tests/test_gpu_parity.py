@@ -692,18 +692,44 @@ def test_multi_gpu_paths_inside_the_library(gpu_solver_factory):
     assert np.array_equal(d_.download(), np.arange(5.0))
 
 
-def test_bench_runs_its_multi_rank_plumbing_without_torch():
-    """bench.py with the N > 1 plumbing forced on one rank (RCCL group of one inside the library, all-gather per step): the
-    JSON line carries value_without_gather, and torch is never imported."""
+def test_bench_runs_its_multi_rank_plumbing_without_torch(tmp_path):
+    """bench.py --full with the N > 1 plumbing forced on one rank (RCCL group of one inside the library, all-gather per step): the
+    JSON line carries value_without_gather, torch is never imported, and the dumped gathered block is the rank's own output."""
     import subprocess
     env = dict(os.environ, MPCB_BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29533")
-    code = ("import sys, runpy; sys.argv = ['bench.py', '--steps', '4', '--warmup', '1', '--batch', '512', '--no-cpu-baseline']; "
-            "runpy.run_path(%r, run_name='__main__'); assert 'torch' not in sys.modules, 'bench.py imported torch'" % os.path.join(os.path.dirname(__file__), "..", "bench.py"))
+    code = ("import sys, runpy; sys.argv = ['bench.py', '--steps', '4', '--warmup', '1', '--batch', '512', '--no-cpu-baseline', '--full', "
+            "'--dump-outputs', %r]; runpy.run_path(%r, run_name='__main__'); assert 'torch' not in sys.modules, 'bench.py imported torch'"
+            % (str(tmp_path), os.path.join(os.path.dirname(__file__), "..", "bench.py")))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     import json
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["config"]["value_without_gather"] > 0 and line["value"] > 0 and "RCCL" in line["config"]["collective"]
+    z = np.load(tmp_path / "z.npy")
+    assert z.shape == (512, 184) and np.array_equal(np.load(tmp_path / "z_gathered.npy"), z)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(gpu_solver_factory, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, leaves out the extra measurements, and --dump-outputs
+    writes what the last timed step returned: with five resident batches, step 3 of 4 solved batch 3 (seed 3), and the
+    host-pointer entry on the same inputs gives the same statuses and trajectories."""
+    import json
+    import subprocess
+    bench = os.path.join(os.path.dirname(__file__), "..", "bench.py")
+    out = subprocess.run([sys.executable, bench, "--steps", "4", "--warmup", "1", "--batch", "512", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=280)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["metric"] == "mpc_solves_per_sec" and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["end_to_end"] is None and "cpu_baseline" not in line
+    d = {k: np.load(tmp_path / (k + ".npy")) for k in ("z", "obj", "status", "iters", "kkt")}
+    assert all(a.dtype == np.float64 for a in d.values())
+    assert d["z"].shape == (512, 184) and d["status"].shape == (512,) and d["kkt"].shape == (512, 4)
+    x0, xs, obs = scenes.sample_c2(512, seed=3)
+    ref = gpu_solver_factory(default_config(model=_abi.MODEL_KIN, N=30, T=0.1, n_obs=1)).solve_batch(x0, xs, obs)
+    assert np.array_equal(d["status"], ref["status"]) and np.array_equal(d["iters"], ref["iters"])
+    assert np.abs(d["z"] - ref["z"]).max() <= 1e-12
 
 
 def test_variable_time_grid_on_device(gpu_solver_factory, oracle_mod, tmp_path, monkeypatch):

@@ -11,7 +11,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-python3 "$ROOT/bench.py" "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 "$ROOT/bench.py" "$@" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench done"; tail -c 600 "$OUT/bench.json"; echo
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 "$ROOT/bench.py" "$@" --no-cpu-baseline > "$OUT/trace.log" 2>&1
 echo "trace done"
