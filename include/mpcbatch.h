@@ -229,6 +229,29 @@ int mpcb_solve_device(mpcb_handle* h, int32_t B,
 #define MPCB_INFLIGHT_MAX 16
 int mpcb_set_inflight(mpcb_handle* h, int32_t k);
 
+/* Per-stage reference tracking.  The reference's stage cost is (X_i - ref_X_i)' Q (X_i - ref_X_i) with
+ * ref_X_i = aa * ref_state[i+1] + (1 - aa) * xs (CMOM/MPC_CBF_optimize_kin.py:194-199); mpcb_solve pins aa = 0, what the reference
+ * ships.  These entries take the blended rows themselves:
+ *   x_ref [B, N, nx]   row i is the point X_i is pulled toward in stage i's cost, i = 0..N-1 (there is no terminal cost); it replaces
+ *                      xs in the objective only: Q, R, the rows and the bounds are those of mpcb_solve.  x_ref == NULL is mpcb_solve /
+ *                      mpcb_solve_device exactly.  A non-finite entry ends that instance with MPCB_ST_NUMERIC, as a non-finite xs does.
+ * Kinematic model, single-device handles: tracking with MPCB_MODEL_DYN (the reference's dyn NLP has no ref_X term,
+ * MPC_CBF_optimize_dyn.py:219) or on a device group (mpcb_set_devices) returns MPCB_E_UNSUPPORTED.
+ * mpcb_solve_ref takes host pointers, mpcb_solve_device_ref device pointers (lane-aware like mpcb_solve_device; results do not depend
+ * on mpcb_set_inflight). */
+int mpcb_solve_ref(mpcb_handle* h, int32_t B,
+                   const double* x0, const double* xs, const double* x_ref,
+                   const double* obs, int32_t obs_kind,
+                   const double* z0,
+                   double* z, double* obj, int32_t* status, int32_t* iters, double* kkt,
+                   double* lam_g, double* lam_x);
+int mpcb_solve_device_ref(mpcb_handle* h, int32_t B,
+                          const double* d_x0, const double* d_xs, const double* d_x_ref,
+                          const double* d_obs, int32_t obs_kind,
+                          const double* d_z0,
+                          double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt,
+                          double* d_lam_g, double* d_lam_x, int32_t sync);
+
 /* Closed loop on the device: `steps` receding-horizon iterations of  solve -> apply U_0 with the plant
  * x0 <- x0 + T f(x0,U_0) -> shift warm start [-> advance obstacles]   (main_cbf_kin_c_sim.py:87-123,16-26;
  * main_cbf_kin_c_sim_pre.py:98-106; with model = MPCB_MODEL_DYN the loop of main_cbf_dyn_c_sim.py:75-108, plant = the dyn
@@ -254,6 +277,15 @@ int mpcb_set_inflight(mpcb_handle* h, int32_t k);
 int mpcb_closed_loop(mpcb_handle* h, int32_t B, int32_t steps,
                      const double* x0, const double* xs, double* obs_state, int32_t obs_motion, int32_t flags,
                      double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist);
+/* mpcb_closed_loop with path tracking, the reference driver's loop with blend weight aa in [0, 1] (main_cbf_kin_c_sim.py:52,98-100):
+ * instance b's straight global path starts at its own initial x0[b, 0] (define_ref_path(x0, xs, T_S)); before every solve the
+ * window of mpcb_ref_path_window is taken at the current state with last_idx (0 at the start) carried on the device, N + 1 points
+ * (N_p = N, T_horizon = N * T, dt = T), and stage i's reference is aa * window[i+1] + (1 - aa) * xs.  aa = 0 gives exactly the
+ * histories of mpcb_closed_loop.  aa outside [0, 1]: MPCB_E_INVALID; MPCB_MODEL_DYN, a device group or a time grid
+ * (mpcb_set_time_grid): MPCB_E_UNSUPPORTED. */
+int mpcb_closed_loop_ref(mpcb_handle* h, int32_t B, int32_t steps,
+                         const double* x0, const double* xs, double* obs_state, int32_t obs_motion, int32_t flags, double aa,
+                         double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist);
 
 /* ---- scene generation on the device -----------------------------------------------------------------------
  * Counter-based random scenes (Philox4x32-10 keyed by `seed`, counter = global scene index): scene i is the same whichever GPU,

@@ -28,8 +28,10 @@ class MPC_optimize(MpcBase):
         return lbg, ubg, lbx, ubx
 
     def optimize_problem(self, ego_state, ref_state, obstacle):
-        # ego_state and ref_state do not enter the reference's NLP (x0 comes in through p; aa = 0, ref :194-197)
+        # ego_state does not enter the reference's NLP (x0 comes in through p); ref_state does only with aa != 0 (ref :194-199)
         obs = None if obstacle is None else np.asarray(obstacle, dtype=np.float64).reshape(-1, 6)
         n_obs = 0 if obs is None else obs.shape[0]
         cfg = self._make_cfg(n_obs)
+        if self.aa != 0:
+            return NlpSolver(self, cfg, None if n_obs == 0 else obs.reshape(1, n_obs, 6), _abi.OBSIN_STATIC, ref_state, self.aa)
         return NlpSolver(self, cfg, None if n_obs == 0 else obs.reshape(1, n_obs, 6), _abi.OBSIN_STATIC)

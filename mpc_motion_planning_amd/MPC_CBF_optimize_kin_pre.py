@@ -27,4 +27,6 @@ class MPC_optimize(MpcBase):
             if traj.shape[1] != self.N_p + 1:
                 raise ValueError("each obstacle trajectory needs N_p + 1 = %d rows" % (self.N_p + 1))
             traj = traj.reshape(1, n_obs, self.N_p + 1, 6)
+        if self.aa != 0:                                   # ref_state enters the stage cost (ref :194-199)
+            return NlpSolver(self, cfg, traj, _abi.OBSIN_PREDICTED, ref_state, self.aa)
         return NlpSolver(self, cfg, traj, _abi.OBSIN_PREDICTED)

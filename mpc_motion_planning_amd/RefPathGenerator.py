@@ -31,8 +31,10 @@ class RefPathGenerator:
         self.ref_len = len(self.ref_global)
         return self.ref_global
 
-    def find_ref_traj(self, x0, xs, T_horizon, dt, last_idx):
-        N_p = int(T_horizon / dt)
+    def find_ref_traj(self, x0, xs, T_horizon, dt, last_idx, N_p=None):
+        # N_p: window length - 1; None = int(T_horizon / dt) as the reference computes it (the tracking closed loop passes N)
+        if N_p is None:
+            N_p = int(T_horizon / dt)
         preview_v = 0.5 * _scalar(x0[3]) + 0.5 * _scalar(xs[3])
         preview_idx = int(preview_v * T_horizon / self.step_x)
         lo = max(0, last_idx - 5)

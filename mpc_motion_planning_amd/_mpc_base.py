@@ -72,12 +72,18 @@ def nlp_constraints(cfg, z, x0, obs, obs_kind):
 class NlpSolver:
     """What `optimize_problem` returns: callable like the object `ca.nlpsol(...)` gives (kin.py:254)."""
 
-    def __init__(self, owner, cfg, obs, obs_kind):
+    def __init__(self, owner, cfg, obs, obs_kind, ref_state=None, aa=0.0):
         self._owner = owner
         self._cfg = cfg
         self._obs = obs
         self._obs_kind = obs_kind
         self._stats = {}
+        # tracking (aa != 0, kin.py:194-199): the (N_p+1, nx) window optimize_problem was given; stage i is pulled toward
+        # aa * ref_state[i+1] + (1 - aa) * xs
+        self._ref = None if ref_state is None else np.asarray(ref_state, dtype=np.float64).reshape(-1, cfg.nx())
+        self._aa = float(aa)
+        if self._ref is not None and self._ref.shape[0] != cfg.N + 1:
+            raise ValueError("ref_state needs N_p + 1 = %d rows, got %d" % (cfg.N + 1, self._ref.shape[0]))
 
     def __call__(self, x0=None, p=None, lbg=None, lbx=None, ubg=None, ubx=None, **_ignored):
         cfg = self._cfg
@@ -91,7 +97,11 @@ class NlpSolver:
         if pv.size != 2 * nx:
             raise ValueError("p must hold [x0; xs] (%d values)" % (2 * nx))
         z0 = None if x0 is None else np.asarray(x0, dtype=np.float64).reshape(1, -1)
-        r = bs.solve_batch(pv[:nx].reshape(1, nx), pv[nx:].reshape(1, nx), self._obs, z0, multipliers=True)
+        if self._ref is None:
+            r = bs.solve_batch(pv[:nx].reshape(1, nx), pv[nx:].reshape(1, nx), self._obs, z0, multipliers=True)
+        else:
+            x_ref = self._aa * self._ref[1:] + (1 - self._aa) * pv[nx:]
+            r = bs.solve_batch(pv[:nx].reshape(1, nx), pv[nx:].reshape(1, nx), self._obs, z0, multipliers=True, x_ref=x_ref[None])
         st = int(r["status"][0])
         self._stats = {"success": st == _abi.ST_SOLVED, "return_status": _RETURN_STATUS.get(st, "Unknown"),
                        "iter_count": int(r["iters"][0]), "status_code": st, "kkt": r["kkt"][0].copy()}
@@ -164,6 +174,9 @@ class MpcBase:
         # < 1 %; on the instances both solve, 92-93 % end at the same trajectory (tests/test_parity_evidence.py).
         self.start = "rollout"
         self.integrator = "euler"                      # "rk4": MPCB_INT_RK4 (kinematic model), NLP rows and plant step alike
+        # Blend weight of the reference path in the stage cost, ref_X_i = aa * ref_state[i+1] + (1 - aa) * xs (kin.py:194-199); the
+        # reference ships 0.0 (pure set-point).  aa != 0 makes optimize_problem(ref_state=...) of the kinematic classes track the window.
+        self.aa = 0.0
         self.f = ModelFunction(self._make_cfg(0))
 
     # ----- configuration of the HIP library from the YAML values ------------------------------------------

@@ -74,6 +74,30 @@ __global__ __launch_bounds__(64, 1) void mpcb_kernel_kin_resto(const MpcbKArgs a
   mpcb_solve_kin<NOBS, GEN, true, RK4>(a, (int)blockIdx.x, mpcb_lds, MPCB_PASS_RESTO);
 }
 
+// per-stage reference tracking (mpcb_solve_ref, a.xref != NULL): the same two kernels with the TRACK instantiation of the solve; the
+// fused second attempt follows the same rule
+template <int NOBS, bool GEN = false, bool RK4 = false>
+__global__ __launch_bounds__(64, MPCB_WAVES_PER_SIMD) void mpcb_track_kin(const MpcbKArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
+  if constexpr (mpcb_kin_fuses<NOBS, GEN, RK4>) {
+    int pass = a.pass;
+#pragma clang loop unroll(disable)
+    for (;;) {
+      mpcb_solve_kin<NOBS, GEN, false, RK4, true>(a, (int)blockIdx.x, mpcb_lds, pass);
+      if (!mpcb_second_attempt_here(a, (int)blockIdx.x, pass)) break;
+      pass = MPCB_PASS_SECOND;
+    }
+  } else {
+    mpcb_solve_kin<NOBS, GEN, false, RK4, true>(a, (int)blockIdx.x, mpcb_lds, a.pass);
+  }
+}
+
+template <int NOBS, bool GEN = false, bool RK4 = false>
+__global__ __launch_bounds__(64, 1) void mpcb_track_kin_resto(const MpcbKArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
+  mpcb_solve_kin<NOBS, GEN, true, RK4, true>(a, (int)blockIdx.x, mpcb_lds, MPCB_PASS_RESTO);
+}
+
 template <int NOBS>
 __global__ __launch_bounds__(64, MPCB_WAVES_PER_SIMD) void mpcb_kernel_dyn(const MpcbKArgs a) {
   extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
@@ -298,6 +322,42 @@ __global__ __launch_bounds__(128) void mpcb_ref_window_kernel(int B, double x_st
   }
 }
 
+// Per-stage reference of the tracking closed loop (mpcb_closed_loop_ref): the window rule of mpcb_ref_window_kernel with the path of
+// instance b starting at its own x_start[b] (its initial x0[b, 0], main_cbf_kin_c_sim.py:52), N_p = N points after the nearest one,
+// T_horizon = N * T, and the blend of the reference's stage cost (kin.py:194-199):  xref[b, i] = aa * window[i + 1] + (1 - aa) * xs[b].
+__global__ __launch_bounds__(128) void mpcb_track_window(int B, int N, double T, double aa, const double* __restrict__ x_start,
+                                                         const double* __restrict__ x0, const double* __restrict__ xs,
+                                                         int32_t* __restrict__ last_idx, double* __restrict__ xref) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const double* e = x0 + (size_t)b * 4; const double* t = xs + (size_t)b * 4;
+  const double xa = x_start[b], T_horizon = N * T;
+  const double step = t[0] > xa ? 1.0 : -1.0;
+  const int M = (int)ceil(((t[0] + step) - xa) / step);
+  const double pv = 0.5 * e[3] + 0.5 * t[3];
+  const int pidx = (int)(pv * T_horizon / 1.0);
+  const int last = last_idx[b];
+  const int lo = last - 5 > 0 ? last - 5 : 0, hi = last + pidx < M ? last + pidx : M;
+  int mi = lo; double best = INFINITY;
+  for (int i = lo; i < hi; ++i) {
+    const double dx = (xa + i * step) - e[0], dy = t[1] - e[1];
+    const double d = sqrt(dx * dx + dy * dy);
+    if (d < best) { best = d; mi = i; } else break;
+  }
+  last_idx[b] = mi;
+  const double lstep = ((double)(mi + pidx) - (double)mi) / (double)N;
+  const double wb = 1.0 - aa;
+  for (int j = 1; j <= N; ++j) {                                                       // window point j is the reference of stage j - 1
+    double v = j == N ? (double)(mi + pidx) : (double)j * lstep + (double)mi;
+    v = v < 0 ? 0 : v > (double)(M - 1) ? (double)(M - 1) : v;
+    const int idx = (int)v;
+    const double w[4] = {xa + idx * step, t[1], t[2], t[3]};
+    double* r = xref + ((size_t)b * N + (j - 1)) * 4;
+    for (int q = 0; q < 4; ++q) r[q] = aa * w[q] + wb * t[q];
+  }
+}
+
 }  // namespace
 
 struct mpcb_handle {
@@ -434,9 +494,9 @@ bool is_gen(const mpcb_config& c) { return c.model == MPCB_MODEL_KIN && c.obs_mo
 bool is_rk4(const mpcb_config& c) { return c.model == MPCB_MODEL_KIN && c.integrator == MPCB_INT_RK4; }
 bool wide_table(const mpcb_config& c) { return is_gen(c) || is_rk4(c); }       // four more rows in the entry table of the kinematic kernels
 
-size_t lds_bytes(const mpcb_config& c, int nz) {
+size_t lds_bytes(const mpcb_config& c, int nz, bool track = false) {
   return (size_t)(c.model == MPCB_MODEL_DYN ? mpcbk::layout_dyn(c.N, false, mpcbk::obs_in_lds(mpcbk::obs_capacity_dyn(c.n_obs))).total
-                                             : mpcbk::layout_kin(c.N, nz, false, mpcbk::obs_in_lds(mpcbk::obs_capacity_kin(c.n_obs, is_gen(c))), wide_table(c)).total) * sizeof(double);
+                                             : mpcbk::layout_kin(c.N, nz, false, mpcbk::obs_in_lds(mpcbk::obs_capacity_kin(c.n_obs, is_gen(c))), wide_table(c), track).total) * sizeof(double);
 }
 
 // oldest recorded pair -> total_ms / last_ms / launches
@@ -513,7 +573,8 @@ int second_mode(const mpcb_config& c, const void* z0) { return c.second_start ==
 // both passes of one solve on lane `lane_id` (0 = the handle's own stream)
 int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   MpcbKArgs a = a_in;
-  const size_t lds = lds_bytes(h->cfg, h->nz);
+  const bool trk = a.xref != nullptr;             // per-stage reference: the mpcb_track_* kernels (kinematic model only, checked by the entry points)
+  const size_t lds = lds_bytes(h->cfg, h->nz, trk);
   if (lds > 160 * 1024) return fail(h, MPCB_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", lds);
   if (a.B == 0) return MPCB_OK;
   if (h->lanes.empty()) { int rc = ensure_lanes(h, 1); if (rc != MPCB_OK) return rc; }
@@ -551,7 +612,21 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   int rc = MPCB_OK;
   auto lean_pass = [&](int pass) -> int {         // the lean main-phase kernel over the whole grid
     a.pass = pass;
-    if (h->cfg.model == MPCB_MODEL_DYN) {
+    if (trk) {
+      if (h->cfg.obs_mode == MPCB_OBS_DCBF && h->cfg.gamma < 1.0 - 1e-12 && n > 0) {
+        if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin<1, true>, a, lds);
+        else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin<3, true>, a, lds);
+        else rc = launch_kernel(h, stream, mpcb_track_kin<8, true>, a, lds);
+      } else if (is_rk4(h->cfg)) {
+        if (n == 0) rc = launch_kernel(h, stream, mpcb_track_kin<0, false, true>, a, lds);
+        else if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin<1, false, true>, a, lds);
+        else rc = launch_kernel(h, stream, mpcb_track_kin<3, false, true>, a, lds);
+      } else if (n == 0) rc = launch_kernel(h, stream, mpcb_track_kin<0>, a, lds);
+      else if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin<1>, a, lds);
+      else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin<3>, a, lds);
+      else if (n <= 5) rc = launch_kernel(h, stream, mpcb_track_kin<5>, a, lds);
+      else rc = launch_kernel(h, stream, mpcb_track_kin<8>, a, lds);
+    } else if (h->cfg.model == MPCB_MODEL_DYN) {
       if (n <= 1) rc = launch_kernel(h, stream, mpcb_kernel_dyn<1>, a, lds);
       else if (n <= 3) rc = launch_kernel(h, stream, mpcb_kernel_dyn<3>, a, lds);
       else if (n <= 5) rc = launch_kernel(h, stream, mpcb_kernel_dyn<5>, a, lds);
@@ -577,10 +652,24 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
     a.pass = MPCB_PASS_RESTO;
     const bool dyn = h->cfg.model == MPCB_MODEL_DYN;
     const size_t lds2 = (size_t)(dyn ? mpcbk::layout_dyn(h->cfg.N, true, mpcbk::obs_in_lds(mpcbk::obs_capacity_dyn(n))).total
-                                     : mpcbk::layout_kin(h->cfg.N, h->nz, true, mpcbk::obs_in_lds(mpcbk::obs_capacity_kin(n, is_gen(h->cfg))), wide_table(h->cfg)).total) * sizeof(double);
+                                     : mpcbk::layout_kin(h->cfg.N, h->nz, true, mpcbk::obs_in_lds(mpcbk::obs_capacity_kin(n, is_gen(h->cfg))), wide_table(h->cfg), trk).total) * sizeof(double);
     if (lds2 > 160 * 1024) return fail(h, MPCB_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", lds2);
     const bool gen = h->cfg.obs_mode == MPCB_OBS_DCBF && h->cfg.gamma < 1.0 - 1e-12 && n > 0;
-    if (dyn) {
+    if (trk) {
+      if (gen) {
+        if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin_resto<1, true>, a, lds2);
+        else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin_resto<3, true>, a, lds2);
+        else rc = launch_kernel(h, stream, mpcb_track_kin_resto<8, true>, a, lds2);
+      } else if (is_rk4(h->cfg)) {
+        if (n == 0) rc = launch_kernel(h, stream, mpcb_track_kin_resto<0, false, true>, a, lds2);
+        else if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin_resto<1, false, true>, a, lds2);
+        else rc = launch_kernel(h, stream, mpcb_track_kin_resto<3, false, true>, a, lds2);
+      } else if (n == 0) rc = launch_kernel(h, stream, mpcb_track_kin_resto<0>, a, lds2);
+      else if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin_resto<1>, a, lds2);
+      else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin_resto<3>, a, lds2);
+      else if (n <= 5) rc = launch_kernel(h, stream, mpcb_track_kin_resto<5>, a, lds2);
+      else rc = launch_kernel(h, stream, mpcb_track_kin_resto<8>, a, lds2);
+    } else if (dyn) {
       if (n <= 1) rc = launch_kernel(h, stream, mpcb_kernel_dyn_resto<1>, a, lds2);
       else if (n <= 3) rc = launch_kernel(h, stream, mpcb_kernel_dyn_resto<3>, a, lds2);
       else if (n <= 5) rc = launch_kernel(h, stream, mpcb_kernel_dyn_resto<5>, a, lds2);
@@ -625,6 +714,13 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   return MPCB_OK;
 }
 
+// what the tracking entry points support: the kinematic model on a single-device handle
+int check_track(mpcb_handle* h) {
+  if (h->cfg.model != MPCB_MODEL_KIN) return fail(h, MPCB_E_UNSUPPORTED, "per-stage reference tracking is built for the kinematic model only");
+  if (!h->peers.empty()) return fail(h, MPCB_E_UNSUPPORTED, "per-stage reference tracking does not run on a device group (mpcb_set_devices)");
+  return MPCB_OK;
+}
+
 int ensure_scratch(mpcb_handle* h, size_t bytes) {
   if (bytes <= h->d_cap) return MPCB_OK;
   if (h->d_buf) { HIP_TRY(h, hipFree(h->d_buf)); h->d_buf = nullptr; h->d_cap = 0; }
@@ -644,7 +740,7 @@ struct Carve {
 // one launch of the solve over B instances, everything resident on the handle's device, asynchronous on its stream
 int solve_on_device(mpcb_handle* h, int32_t B, const double* d_x0, const double* d_xs, const double* d_obs, int32_t obs_kind,
                     const double* d_z0, double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, int32_t st_stride,
-                    double* d_kkt, double* d_lam_g, double* d_lam_x, int lane_id = 0) {
+                    double* d_kkt, double* d_lam_g, double* d_lam_x, int lane_id = 0, const double* d_xref = nullptr) {
   if (B < 0 || !d_x0 || !d_xs || !d_z) return fail(h, MPCB_E_INVALID, "B < 0 or a required pointer is NULL");
   if (h->cfg.n_obs > 0 && !d_obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
   if (obs_kind != MPCB_OBSIN_STATIC && obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", obs_kind);
@@ -654,6 +750,7 @@ int solve_on_device(mpcb_handle* h, int32_t B, const double* d_x0, const double*
   a.want_mult = (d_lam_g || d_lam_x) ? 1 : 0; a.trace_instance = -1; a.trace = nullptr; a.st_stride = st_stride; a.tgrid = h->d_tgrid;
   a.x0 = d_x0; a.xs = d_xs; a.obs = d_obs; a.z0 = d_z0;
   a.z = d_z; a.obj = d_obj; a.kkt = d_kkt; a.lam_g = d_lam_g; a.lam_x = d_lam_x; a.status = d_status; a.iters = d_iters;
+  a.xref = d_xref;
   return launch_solve(h, a, lane_id);
 }
 
@@ -664,18 +761,18 @@ int solve_on_device(mpcb_handle* h, int32_t B, const double* d_x0, const double*
 // into chunks: 5.5 ms per call against 4.2 ms for the single launch — so the host-pointer entries stay one launch on lane 0.
 int solve_next_lane(mpcb_handle* h, int32_t B, const double* d_x0, const double* d_xs, const double* d_obs, int32_t obs_kind,
                     const double* d_z0, double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt,
-                    double* d_lam_g, double* d_lam_x) {
+                    double* d_lam_g, double* d_lam_x, const double* d_xref = nullptr) {
   const int K = h->lanes.empty() ? 1 : (int)h->lanes.size();
   const int lane = K == 1 ? 0 : h->next_lane;
   if (K > 1) h->next_lane = (h->next_lane + 1) % K;
-  return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, 1, d_kkt, d_lam_g, d_lam_x, lane);
+  return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, 1, d_kkt, d_lam_g, d_lam_x, lane, d_xref);
 }
 
 }  // namespace
 
 extern "C" {
 
-const char* mpcb_version(void) { return "mpcbatch 0.3 (gfx950, abi 3)"; }
+const char* mpcb_version(void) { return "mpcbatch 0.4 (gfx950, abi 3)"; }
 
 int mpcb_default_config(mpcb_config* cfg, int32_t model, int32_t N, double T) {
   if (!cfg || (model != MPCB_MODEL_KIN && model != MPCB_MODEL_DYN)) return MPCB_E_INVALID;
@@ -875,6 +972,17 @@ int mpcb_solve_device(mpcb_handle* h, int32_t B, const double* d_x0, const doubl
   return MPCB_OK;
 }
 
+int mpcb_solve_device_ref(mpcb_handle* h, int32_t B, const double* d_x0, const double* d_xs, const double* d_x_ref, const double* d_obs,
+                          int32_t obs_kind, const double* d_z0, double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt,
+                          double* d_lam_g, double* d_lam_x, int32_t sync) {
+  if (!h) return MPCB_E_INVALID;
+  if (d_x_ref) { int rc = check_track(h); if (rc != MPCB_OK) return rc; }
+  int rc = solve_next_lane(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, d_kkt, d_lam_g, d_lam_x, d_x_ref);
+  if (rc != MPCB_OK) return rc;
+  if (sync) return mpcb_sync(h);
+  return MPCB_OK;
+}
+
 int mpcb_set_inflight(mpcb_handle* h, int32_t k) {
   if (!h) return MPCB_E_INVALID;
   if (k < 1 || k > MPCB_INFLIGHT_MAX) return fail(h, MPCB_E_INVALID, "inflight = %d outside 1..%d", k, MPCB_INFLIGHT_MAX);
@@ -894,6 +1002,7 @@ struct HostSolve {
   mpcb_handle* h; int32_t B; int obs_kind;
   const double *x0, *xs, *obs, *z0; double *z, *obj, *kkt, *lam_g, *lam_x; int32_t *status, *iters;
   double *d_x0, *d_xs, *d_obs, *d_z0, *d_z, *d_obj, *d_kkt, *d_lg, *d_lx; int32_t *d_st, *d_it;
+  const double* xref = nullptr; double* d_xr = nullptr;        // [B, N, 4] per-stage reference (mpcb_solve_ref), NULL = the set-point solve
   int issue() {
     HIP_TRY(h, hipSetDevice(h->device));
     { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
@@ -911,15 +1020,17 @@ struct HostSolve {
       d_lx = lam_x ? cv.take<double>((size_t)B * nz) : nullptr;
       d_st = cv.take<int32_t>(B);
       d_it = cv.take<int32_t>(B);
+      d_xr = xref ? cv.take<double>((size_t)B * N * 4) : nullptr;
     };
     { Carve dry{nullptr}; carve(dry); int rc = ensure_scratch(h, dry.bytes()); if (rc != MPCB_OK) return rc; }
     { Carve cv{(char*)h->d_buf}; carve(cv); }
     hipStream_t s = h->stream;
+    if (d_xr) HIP_TRY(h, hipMemcpyAsync(d_xr, xref, (size_t)B * N * 4 * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(d_x0, x0, (size_t)B * nx * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(d_xs, xs, (size_t)B * nx * 8, hipMemcpyHostToDevice, s));
     if (d_obs) HIP_TRY(h, hipMemcpyAsync(d_obs, obs, n_obs_d * 8, hipMemcpyHostToDevice, s));
     if (d_z0) HIP_TRY(h, hipMemcpyAsync(d_z0, z0, (size_t)B * nz * 8, hipMemcpyHostToDevice, s));
-    return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_st, d_it, 1, d_kkt, d_lg, d_lx);
+    return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_st, d_it, 1, d_kkt, d_lg, d_lx, 0, d_xr);
   }
   int collect() {
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1037,6 +1148,26 @@ int mpcb_solve(mpcb_handle* h, int32_t B, const double* x0, const double* xs, co
   return MPCB_OK;
 }
 
+int mpcb_solve_ref(mpcb_handle* h, int32_t B, const double* x0, const double* xs, const double* x_ref, const double* obs, int32_t obs_kind,
+                   const double* z0, double* z, double* obj, int32_t* status, int32_t* iters, double* kkt, double* lam_g, double* lam_x) {
+  if (!h) return MPCB_E_INVALID;
+  if (!x_ref) return mpcb_solve(h, B, x0, xs, obs, obs_kind, z0, z, obj, status, iters, kkt, lam_g, lam_x);
+  { int rc = check_track(h); if (rc != MPCB_OK) return rc; }
+  if (B < 0 || !x0 || !xs || !z) return fail(h, MPCB_E_INVALID, "B < 0 or a required pointer is NULL");
+  if (h->cfg.n_obs > 0 && !obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
+  if (obs_kind != MPCB_OBSIN_STATIC && obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", obs_kind);
+  if (B == 0) return MPCB_OK;
+  HostSolve q{};
+  q.h = h; q.B = B; q.obs_kind = obs_kind; q.x0 = x0; q.xs = xs; q.obs = obs; q.z0 = z0; q.xref = x_ref;
+  q.z = z; q.obj = obj; q.kkt = kkt; q.lam_g = lam_g; q.lam_x = lam_x; q.status = status; q.iters = iters;
+  int rc = q.issue();
+  if (rc != MPCB_OK) return rc;
+  rc = q.collect();
+  if (rc != MPCB_OK) return rc;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MPCB_OK;
+}
+
 int mpcb_solve_trace(mpcb_handle* h, const double* x0, const double* xs, const double* obs, int32_t obs_kind, const double* z0,
                      double* z, int32_t* status, int32_t* iters, double* trace) {
   if (!h || !x0 || !xs || !z || !trace) return fail(h, MPCB_E_INVALID, "NULL argument");
@@ -1066,7 +1197,7 @@ int mpcb_solve_trace(mpcb_handle* h, const double* x0, const double* xs, const d
   MpcbKArgs a;
   a.cfg = h->cfg; a.B = 1; a.nz = nz; a.ng = h->ng; a.obs_kind = obs_kind; a.want_mult = 0; a.trace_instance = 0; a.trace = d_tr; a.st_stride = 1; a.tgrid = h->d_tgrid;
   a.x0 = d_x0; a.xs = d_xs; a.obs = d_obs; a.z0 = d_z0; a.z = d_z; a.obj = nullptr; a.kkt = nullptr; a.lam_g = nullptr; a.lam_x = nullptr;
-  a.status = d_st; a.iters = d_it;
+  a.status = d_st; a.iters = d_it; a.xref = nullptr;
   rc = launch_solve(h, a);
   if (rc != MPCB_OK) return rc;
   HIP_TRY(h, hipMemcpyAsync(z, d_z, nz * 8, hipMemcpyDeviceToHost, s));
@@ -1080,7 +1211,8 @@ int mpcb_solve_trace(mpcb_handle* h, const double* x0, const double* xs, const d
 // the closed loop; scenes either come from the host (x0, xs, obs_state) or are drawn on the device (sample_kind != 0)
 static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const double* x0, const double* xs, double* obs_state, int32_t obs_motion,
                             int32_t flags, double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist,
-                            int32_t sample_kind, uint64_t seed, uint64_t first_index, double* x0_out, double* obs0_out) {
+                            int32_t sample_kind, uint64_t seed, uint64_t first_index, double* x0_out, double* obs0_out,
+                            bool track = false, double aa = 0.0) {
   if (!h) return MPCB_E_INVALID;
   if (B < 0 || steps < 0 || (!sample_kind && (!x0 || !xs))) return fail(h, MPCB_E_INVALID, "B < 0, steps < 0 or a required pointer is NULL");
   if (!sample_kind && h->cfg.n_obs > 0 && !obs_state) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs_state is NULL", h->cfg.n_obs);
@@ -1093,6 +1225,7 @@ static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const doub
   const int nx = h->nx, nz = h->nz, N = h->cfg.N, no = h->cfg.n_obs;
   const size_t n_traj = predict ? (size_t)B * no * (N + 1) * 6 : 0;
   double *d_x0, *d_xs, *d_obs, *d_traj, *d_z0, *d_z, *d_xh, *d_uh; int32_t *d_st, *d_it;
+  double *d_xr = nullptr, *d_xa = nullptr; int32_t* d_li = nullptr;      // tracking: [B, N, 4] reference, path start and last_idx per instance
   auto carve = [&](Carve& cv) {
     d_x0 = cv.take<double>((size_t)B * nx);
     d_xs = cv.take<double>((size_t)B * nx);
@@ -1104,6 +1237,7 @@ static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const doub
     d_uh = cv.take<double>((size_t)B * steps * 2);
     d_st = cv.take<int32_t>((size_t)B * steps);
     d_it = cv.take<int32_t>((size_t)B * steps);
+    if (track) { d_xr = cv.take<double>((size_t)B * N * 4); d_xa = cv.take<double>(B); d_li = cv.take<int32_t>(B); }
   };
   { Carve dry{nullptr}; carve(dry); int rc = ensure_scratch(h, dry.bytes()); if (rc != MPCB_OK) return rc; }
   { Carve cv{(char*)h->d_buf}; carve(cv); }
@@ -1120,6 +1254,10 @@ static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const doub
   }
   HIP_TRY(h, hipMemsetAsync(d_z0, 0, (size_t)B * nz * 8, s));                  // u0 = 0, next_states = 0 (main_cbf_kin_c_sim.py:47-50)
   HIP_TRY(h, hipMemcpy2DAsync(d_xh, (size_t)(steps + 1) * nx * 8, d_x0, (size_t)nx * 8, (size_t)nx * 8, B, hipMemcpyDeviceToDevice, s));
+  if (track) {           // define_ref_path(x0, xs, T_S) once per instance (main_cbf_kin_c_sim.py:52), last_idx = 0
+    HIP_TRY(h, hipMemcpy2DAsync(d_xa, 8, d_x0, (size_t)nx * 8, 8, B, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(h, hipMemsetAsync(d_li, 0, (size_t)B * 4, s));
+  }
   const int move = obs_motion == MPCB_OBSMOVE_STATIC ? 0 : (flags & MPCB_CL_ADVANCE_FIRST_ONLY) ? 2 : 1;
   const int hold = (flags & MPCB_CL_HOLD_ON_FAILURE) ? 1 : 0;
   const double Tstep = h->d_tgrid ? h->T0 : h->cfg.T;
@@ -1130,8 +1268,12 @@ static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const doub
       hipLaunchKernelGGL(mpcb_predict_obs, dim3((total + 255) / 256), dim3(256), 0, s, total, N, h->cfg.T, h->d_tgrid, d_obs, d_traj);
       obs_in = d_traj; kind = MPCB_OBSIN_PREDICTED;
     }
+    if (track) {         // find_ref_traj at the current state (main_cbf_kin_c_sim.py:98-99), blended into the stage references
+      hipLaunchKernelGGL(mpcb_track_window, dim3((B + 127) / 128), dim3(128), 0, s, B, N, h->cfg.T, aa, d_xa, d_x0, d_xs, d_li, d_xr);
+      HIP_TRY(h, hipGetLastError());
+    }
     // the solve kernel writes status / iters of step t straight into column t of the [B, steps] histories
-    int rc = solve_on_device(h, B, d_x0, d_xs, obs_in, kind, d_z0, d_z, nullptr, d_st + t, d_it + t, steps, nullptr, nullptr, nullptr);
+    int rc = solve_on_device(h, B, d_x0, d_xs, obs_in, kind, d_z0, d_z, nullptr, d_st + t, d_it + t, steps, nullptr, nullptr, nullptr, 0, d_xr);
     if (rc != MPCB_OK) return rc;
     if (nx == 6)
       hipLaunchKernelGGL(mpcb_advance<6>, dim3((B + 127) / 128), dim3(128), 0, s, h->cfg, B, nz, d_z, d_x0, d_z0, d_obs, d_xh, d_uh,
@@ -1153,6 +1295,17 @@ static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const doub
 int mpcb_closed_loop(mpcb_handle* h, int32_t B, int32_t steps, const double* x0, const double* xs, double* obs_state, int32_t obs_motion,
                      int32_t flags, double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist) {
   return closed_loop_impl(h, B, steps, x0, xs, obs_state, obs_motion, flags, x_hist, u_hist, status_hist, iters_hist, 0, 0, 0, nullptr, nullptr);
+}
+
+int mpcb_closed_loop_ref(mpcb_handle* h, int32_t B, int32_t steps, const double* x0, const double* xs, double* obs_state, int32_t obs_motion,
+                         int32_t flags, double aa, double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist) {
+  if (!h) return MPCB_E_INVALID;
+  if (!(aa >= 0.0 && aa <= 1.0)) return fail(h, MPCB_E_INVALID, "aa = %g outside [0, 1]", aa);
+  { int rc = check_track(h); if (rc != MPCB_OK) return rc; }
+  if (h->d_tgrid) return fail(h, MPCB_E_UNSUPPORTED, "the tracking closed loop samples its path window on the uniform grid cfg.T: no time grid");
+  if (aa == 0.0)         // every stage reference is xs: the set-point loop itself
+    return closed_loop_impl(h, B, steps, x0, xs, obs_state, obs_motion, flags, x_hist, u_hist, status_hist, iters_hist, 0, 0, 0, nullptr, nullptr);
+  return closed_loop_impl(h, B, steps, x0, xs, obs_state, obs_motion, flags, x_hist, u_hist, status_hist, iters_hist, 0, 0, 0, nullptr, nullptr, true, aa);
 }
 
 int mpcb_closed_loop_sampled(mpcb_handle* h, int32_t kind, int32_t B, uint64_t seed, uint64_t first_index, int32_t steps, int32_t obs_motion,

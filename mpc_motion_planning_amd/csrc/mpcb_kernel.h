@@ -44,6 +44,7 @@ struct MpcbKArgs {
   double *z, *obj, *kkt, *lam_g, *lam_x;
   int32_t *status, *iters;
   double* trace;   // optional: [max_iter + 1][8] log of instance trace_instance (debug / parity tests)
+  const double* xref;  // [B][N][4] per-stage reference of the tracking kernels (mpcb_solve_ref): row i replaces xs in stage i's cost; NULL elsewhere
 };
 
 // MPCB_STAMPS (diagnostic build only, never shipped): overwrite trace columns 4..7 with cycle counts of the phases of
@@ -117,14 +118,15 @@ constexpr int FWR = 8, FWS = 50, FW_C0 = 6, FW_BX = 7, FW_PAD = 48, FW_ZERO = 1,
 // instead of holding ~25 SGPR pairs through the whole solve
 constexpr int CS_WQ = 0, CS_WR = 4, CS_WDR = 6, CS_Q = 8, CS_R = 12, CS_DR = 14, CS_UL = 16, CS_XS = 18, CS_ACC = 24, CSZ = 26;   // CS_ACC: state of the acceptable-point test (objective at the previous check, iterations in a row)
 struct Layout {
-  int ld, ent, Pst, fw, W, cst, filt, zbuf, ct, obl, total;
+  int ld, ent, Pst, fw, W, cst, filt, zbuf, ct, obl, trk, total;
 };
 // obstacle-row capacity of the kernel instantiation that serves n obstacles, and how many of its obstacle constants (centre, 1/sX^2,
 // 1/sY^2: four doubles per obstacle and lane) live in LDS instead of registers: none up to 3, all of them above (the 5- and
 // 8-obstacle instantiations are far beyond the register file otherwise)
 MPCB_HD int obs_capacity_kin(int n, bool gen = false) { return n <= 0 ? (gen ? 1 : 0) : n == 1 ? 1 : n <= 3 ? 3 : (n <= 5 && !gen) ? 5 : 8; }   // (no GEN<5> instantiation)
 MPCB_HD int obs_in_lds(int capacity) { return capacity > 3 ? capacity : 0; }
-MPCB_HD Layout layout_kin(int N, int nz, bool resto = false, int nobl = 0, bool gen = true) {
+// trk: the tracking kernels' per-stage reference, [4][N+2] (lane = node as in the cost table; columns N and N+1 hold xs)
+MPCB_HD Layout layout_kin(int N, int nz, bool resto = false, int nobl = 0, bool gen = true, bool track = false) {
   Layout L;
   const int N1 = N + 1;
   L.ld = N1 | 1;
@@ -139,6 +141,7 @@ MPCB_HD Layout layout_kin(int N, int nz, bool resto = false, int nobl = 0, bool 
   (void)nz;
   L.ct = o; if (resto) o += CT_ROWS * (N + 2);
   L.obl = o; o += 4 * nobl * (N + 2);
+  L.trk = o; if (track) o += 4 * (N + 2);
   L.total = o;
   return L;
 }
@@ -288,7 +291,10 @@ constexpr double DW_FIRST = 1e-4, DW_MIN = 1e-20, DW_MAX = 1e40, KW_MINUS = 1.0 
 // flag, per-node cost table, elastic obstacle rows.  The RESTO = false instantiation is the lean main phase of the first pass.
 // RK4 = the shooting rows use the Runge-Kutta step (cfg.integrator = MPCB_INT_RK4; keep-out / gamma = 1 rows only, never with GEN): the
 //   stage's B block becomes dense (the control enters x+, y+ and phi+ through both columns), four more Hessian pairs exist.
-template <int NOBS, bool GEN = false, bool RESTO = false, bool RK4 = false>
+// TRACK = per-stage reference tracking (mpcb_solve_ref): stage i's cost is (X_i - r_i)' Q (X_i - r_i) with r_i = a.xref[b][i] instead of
+//   xs (kin.py:194-199 with ref_X_i = aa * ref_state[i+1] + (1 - aa) * xs).  The reference lives in LDS (layout row block `trk`), read per
+//   lane where the other kernels read the uniform set-point; the Hessian is unchanged.
+template <int NOBS, bool GEN = false, bool RESTO = false, bool RK4 = false, bool TRACK = false>
 MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, const int pass) {   // pass: MPCB_PASS_* (see MpcbKArgs::pass; a parameter of its own because one launch can run two passes of an instance)
   // every kernel argument is read through a pointer the optimiser cannot see through (wv::late_args): the compiler then loads a field
   // where the code needs it instead of preloading the whole 800-byte argument block into scalar registers at entry, most of which it
@@ -307,6 +313,14 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
     if (st1 == MPCB_ST_SOLVED || st1 == MPCB_ST_ACCEPTABLE || st1 == MPCB_ST_INFEASIBLE_X0) return;
     bool fin = true;                                    // non-finite inputs: the first attempt's verdict (at iteration 0) stands
     for (int i = 0; i < 4; ++i) fin = fin && isfinite(a.x0[(size_t)b * 4 + i]) && isfinite(a.xs[(size_t)b * 4 + i]);
+    if constexpr (TRACK) {                              // ... and of the per-stage reference, lane k its row k
+      bool bad = false;
+      if (lane < N) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bad = bad || !isfinite(a.xref[((size_t)b * N + lane) * 4 + i]);
+      }
+      fin = fin && !wv::any(bad);
+    }
     if (!fin) return;
   }
   // Which start does this solve run from?  First attempt: the caller's z0, with X rolled out from x0 (cfg.init_rollout).  Second
@@ -316,7 +330,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
   const bool zeros_start = RESTO ? (a.work && a.work[(size_t)b * mpcbk::WK_SIZE + mpcbk::WK_START] != 0.0) : pass == MPCB_PASS_SECOND;
   const bool rollout = c.init_rollout && !zeros_start;
   constexpr bool OBL = NOBS > 3;                  // obstacle constants in LDS ([4 * j + q][lane]) instead of registers
-  const Layout L = layout_kin(N, nz, RESTO, obs_in_lds(NOBS), GEN || RK4);
+  const Layout L = layout_kin(N, nz, RESTO, obs_in_lds(NOBS), GEN || RK4, TRACK);
   const int ld = L.ld;
   double* ent = lds + L.ent;
   // step length of this lane's stage: cfg.T, or the stage's entry of the time grid (lanes past the last stage take its value)
@@ -381,6 +395,25 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
 #pragma unroll
   for (int i = 0; i < NX; ++i) { X[i] = isnode ? zbuf[NU * N + NX * k + i] : 0.0; lam[i] = 0.0; }
   wv::sync();
+  // tracking reference: the [N][4] row of the instance (coalesced) -> [4][N+2] (lane = node); columns N, N+1 (no stage cost there) hold xs
+  // (cRX re-forms its column from an opaque lane index at every read: a per-lane address kept live through the solve costs the RESTO
+  // instantiations registers they do not have.  `if constexpr` everywhere: the other kernels must not even see the barrier, it moves
+  // the compiler's inlining decisions)
+  double* trk = lds + L.trk;
+  const int tks = N + 2, tkl = lane <= N ? lane : N + 1;
+  auto cRX = [&](int i) -> double {
+    if constexpr (TRACK) { const int l = wv::opaque(wv::lane()); return trk[i * tks + (l <= N ? l : N + 1)]; }
+    else return 0.0;
+  };
+  if constexpr (TRACK) {
+    const double* gxr = wv::late_args(a)->xref + (size_t)b * N * NX;
+    for (int i = lane; i < N * NX; i += 64) trk[(i & 3) * tks + (i >> 2)] = gxr[i];
+    if (lane >= N) {
+#pragma unroll
+      for (int i = 0; i < NX; ++i) trk[i * tks + tkl] = xs[i];
+    }
+    wv::sync();
+  }
 
   // objective scaling at the user's start (gradient-based, nlp_scaling_max_gradient)
   double os;
@@ -391,7 +424,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
     for (int i = 0; i < NU; ++i) { Un[i] = wv::shfl(U[i], k + 1); Up[i] = wv::shfl(U[i], k - 1); }
     if (hasu) {
 #pragma unroll
-      for (int i = 0; i < NX; ++i) g = fmax(g, fabs(2 * c.Q[i] * (X[i] - xs[i])));
+      for (int i = 0; i < NX; ++i) g = fmax(g, fabs(2 * c.Q[i] * (X[i] - (TRACK ? cRX(i) : xs[i]))));
 #pragma unroll
       for (int i = 0; i < NU; ++i) {
         double gu = 2 * c.R[i] * U[i];
@@ -431,7 +464,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
   double osc = os;                       // scale of the running phase's objective: os, or 1 in the restoration phase
   bool rs = false;                       // restoration phase active
   auto cWQ = [&](int i) { return RESTO ? ct[(CT_WQ + i) * cts + ctl] : cst[CS_WQ + i]; };
-  auto cXS = [&](int i) { return RESTO ? ct[(CT_XR + i) * cts + ctl] : cst[CS_XS + i]; };
+  auto cXS = [&](int i) { return RESTO ? ct[(CT_XR + i) * cts + ctl] : TRACK ? cRX(i) : cst[CS_XS + i]; };
   auto cQQ = [&](int i) { return RESTO ? ct[(CT_QQ + i) * cts + ctl] : cst[CS_Q + i]; };
   auto cWR = [&](int i) { return RESTO ? ct[(CT_WR + i) * cts + ctl] : cst[CS_WR + i]; };
   auto cRR = [&](int i) { return RESTO ? ct[(CT_RR + i) * cts + ctl] : cst[CS_R + i]; };
@@ -443,7 +476,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
         ct[(CT_WQ + i) * cts + ctl] = hasu ? os * 2 * c.Q[i] : 0.0; ct[(CT_QQ + i) * cts + ctl] = hasu ? c.Q[i] : 0.0;
-        ct[(CT_XR + i) * cts + ctl] = xs[i];
+        ct[(CT_XR + i) * cts + ctl] = TRACK ? cRX(i) : xs[i];
       }
 #pragma unroll
       for (int i = 0; i < NU; ++i) {
@@ -844,6 +877,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
 #pragma clang loop unroll(disable)
     for (;;) {
       if (++trips > 3 * c.max_iter + 50) { status = MPCB_ST_RESTO_FAILED; break; }   // (phase changes do not count as iterations)
+      if (TRACK && !isfinite(fval)) { status = MPCB_ST_NUMERIC; break; }             // a non-finite reference entry: the objective at the start already is
       if (RESTO && enter && n_rcalls >= RS_MAX_CALLS) { status = MPCB_ST_RESTO_FAILED; break; }
       if (RESTO && enter) {
         ++n_rcalls;
@@ -1026,7 +1060,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
           if (rr_on) dist(qR, sR);
           if (hasu) {      // kin.py:195-205 with the main phase's constants
 #pragma unroll
-            for (int i = 0; i < NX; ++i) { const double e = X[i] - cst[CS_XS + i]; fm += cst[CS_Q + i] * e * e; }
+            for (int i = 0; i < NX; ++i) { const double e = X[i] - (TRACK ? cRX(i) : cst[CS_XS + i]); fm += cst[CS_Q + i] * e * e; }
             fm += cst[CS_R] * U[0] * U[0] + cst[CS_R + 1] * U[1] * U[1];
             if (k > 0 || c.du0_cost) {
               const double d0 = U[0] - (k ? Up0 : cst[CS_UL]), d1 = U[1] - (k ? Up1 : cst[CS_UL + 1]);
@@ -1695,7 +1729,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
       }
       const double At[NX] = {ln[0], ln[1], a02 * ln[0] + a12 * ln[1] + ln[2], a03 * ln[0] + a13 * ln[1] + a23 * ln[2] + ln[3]};
 #pragma unroll
-      for (int i = 0; i < NX; ++i) out[i] = -2 * c.Q[i] * (X[i] - xs[i]) - At[i] / os;
+      for (int i = 0; i < NX; ++i) out[i] = -2 * c.Q[i] * (X[i] - (TRACK ? cRX(i) : xs[i])) - At[i] / os;
     }
     if (rr_on) out[r_rate + (k - 1)] = -item_y(qR, iR) / os;
     if (isnode) {

@@ -1,11 +1,12 @@
 """Closed-loop simulation, one static obstacle — counterpart of
 CasaDi_MPC_Optimize_Multishoot/main_cbf_kin_c_sim.py (same scene constants :45,49,55,68, same loop :87-123).
 
-    python -m mpc_motion_planning_amd.sim.main_cbf_kin_c_sim [--device-loop] [--out run.npz]
+    python -m mpc_motion_planning_amd.sim.main_cbf_kin_c_sim [--device-loop] [--aa 0.5] [--out run.npz]
 
 Default: the reference's flow step by step through the drop-in surface (optimize_problem -> solver -> shift_movement).
 --device-loop: the same 80 steps inside one mpcb_closed_loop call (no host round trips).  Figures are out of scope;
 the histories go to an .npz file.
+--aa: blend weight of the reference path window in the stage cost (kin.py:194-199; the reference ships 0.0).
 """
 import argparse
 import time
@@ -21,11 +22,13 @@ def main(argv=None):
     ap.add_argument("--device-loop", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--sim-time", type=float, default=8.0)
+    ap.add_argument("--aa", type=float, default=0.0, help="path-tracking blend weight in [0, 1] (0: set-point only)")
     args = ap.parse_args(argv)
 
     cfg = load_config(find_params_file())
     T_horizon, T_S = cfg["mpc_params"]["horizon"], cfg["mpc_params"]["T_S"]
     mpc = MPC_CBF_optimize_kin.MPC_optimize()
+    mpc.aa = args.aa
     N_p, n_states, n_controls = mpc.N_p, mpc.num_states, mpc.num_controls
     x0 = np.array([0, 3, 0, 15], dtype=float).reshape(-1, 1)
     xs = np.array([400, 3.5, 0, 30], dtype=float).reshape(-1, 1)
@@ -35,7 +38,7 @@ def main(argv=None):
     if args.device_loop:
         bs = mpc._batch_solver(mpc._make_cfg(1))
         t0 = time.time()
-        r = bs.closed_loop(x0.T, xs.T, obs[None], steps=steps)            # obstacles stay put, as in the reference's loop
+        r = bs.closed_loop(x0.T, xs.T, obs[None], steps=steps, aa=args.aa)   # obstacles stay put, as in the reference's loop
         print("device loop: %d steps in %.1f ms, statuses %s" % (steps, 1e3 * (time.time() - t0), np.bincount(r["status"][0], minlength=5)))
         xh, uh = r["x_hist"][0], r["u_hist"][0]
     else:

@@ -141,13 +141,18 @@ class BatchSolver:
             return obs.reshape(B, n, self.N + 1, 6), _abi.OBSIN_PREDICTED
         raise ValueError("obs has %d values; expected [B,%d,6] or [B,%d,%d,6]" % (obs.size, n, n, self.N + 1))
 
-    def solve_batch(self, x0, xs, obs=None, z0=None, multipliers=False):
-        """x0, xs [B,nx]; obs [B,n_obs,6] | [B,n_obs,N+1,6]; z0 [B,nz] | None  ->  dict(z, obj, status, iters, kkt[, lam_g, lam_x])"""
+    def solve_batch(self, x0, xs, obs=None, z0=None, multipliers=False, x_ref=None):
+        """x0, xs [B,nx]; obs [B,n_obs,6] | [B,n_obs,N+1,6]; z0 [B,nz] | None  ->  dict(z, obj, status, iters, kkt[, lam_g, lam_x])
+        x_ref [B,N,nx] | None: per-stage reference, row i replaces xs in stage i's cost (mpcb_solve_ref; kinematic model only)."""
         x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
         xs = np.ascontiguousarray(np.atleast_2d(np.asarray(xs, dtype=np.float64)))
         B = x0.shape[0]
         if x0.shape != (B, self.nx) or xs.shape != (B, self.nx):
             raise ValueError("x0 and xs must be [B,%d]" % self.nx)
+        if x_ref is not None:
+            x_ref = np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64))
+            if x_ref.shape != (B, self.N, self.nx):
+                raise ValueError("x_ref must be [B,N,nx] = [%d,%d,%d], got %s" % (B, self.N, self.nx, x_ref.shape))
         obs, kind = self._obs(obs, B)
         if z0 is not None:
             z0 = np.ascontiguousarray(np.asarray(z0, dtype=np.float64).reshape(B, self.nz))
@@ -155,8 +160,12 @@ class BatchSolver:
         kkt = np.empty((B, 4))
         lam_g = np.empty((B, self.ng)) if multipliers else None
         lam_x = np.empty((B, self.nz)) if multipliers else None
-        check(lib().mpcb_solve(self._h, B, dptr(x0), dptr(xs), dptr(obs), kind, dptr(z0), dptr(z), dptr(obj), iptr(st),
-                               iptr(it), dptr(kkt), dptr(lam_g), dptr(lam_x)), self._h)
+        if x_ref is None:
+            check(lib().mpcb_solve(self._h, B, dptr(x0), dptr(xs), dptr(obs), kind, dptr(z0), dptr(z), dptr(obj), iptr(st),
+                                   iptr(it), dptr(kkt), dptr(lam_g), dptr(lam_x)), self._h)
+        else:
+            check(lib().mpcb_solve_ref(self._h, B, dptr(x0), dptr(xs), dptr(x_ref), dptr(obs), kind, dptr(z0), dptr(z), dptr(obj),
+                                       iptr(st), iptr(it), dptr(kkt), dptr(lam_g), dptr(lam_x)), self._h)
         out = dict(z=z, obj=obj, status=st, iters=it, kkt=kkt)
         if multipliers:
             out["lam_g"] = lam_g; out["lam_x"] = lam_x
@@ -174,24 +183,33 @@ class BatchSolver:
         return dict(z=z[0], status=int(st[0]), iters=int(it[0]), trace=tr[: int(it[0]) + 1])
 
     def closed_loop(self, x0, xs, obs_state=None, steps=80, obs_motion=_abi.OBSMOVE_STATIC, hold_on_failure=False,
-                    advance_first_only=False):
+                    advance_first_only=False, aa=0.0):
         """Receding-horizon loop on the device (main_cbf_kin_c_sim.py:87-123).  obs_motion: OBSMOVE_STATIC (obstacles fixed,
         main_cbf_kin_c_sim.py), OBSMOVE_PREDICTED (constant-velocity obstacles predicted per solve and advanced per step,
         main_cbf_kin_c_sim_pre.py), OBSMOVE_CURRENT (advanced, no prediction).
         hold_on_failure: a step whose solve fails applies the previous plan (hold-and-shift) instead of the failed iterate.
         advance_first_only: only obstacle 0 moves between steps (main_cbf_kin_c_sim_pre.py:106).
+        aa: blend weight of the path window in the stage cost (kin.py:194-199, mpcb_closed_loop_ref); 0 = the set-point loop.
         Returns dict(x_hist, u_hist, status, iters, obs_state)."""
         x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
         xs = np.ascontiguousarray(np.atleast_2d(np.asarray(xs, dtype=np.float64)))
         B = x0.shape[0]
+        aa = float(aa)
+        if aa != 0.0:
+            if x0.shape != (B, self.nx) or xs.shape != (B, self.nx):
+                raise ValueError("x0 and xs must be [B,%d]" % self.nx)
         ob = None
         if self.cfg.n_obs:
             ob = np.array(obs_state, dtype=np.float64).reshape(B, self.cfg.n_obs, 6).copy()
         xh = np.empty((B, steps + 1, self.nx)); uh = np.empty((B, steps, 2))
         st = np.empty((B, steps), np.int32); it = np.empty((B, steps), np.int32)
         flags = (_abi.CL_HOLD_ON_FAILURE if hold_on_failure else 0) | (_abi.CL_ADVANCE_FIRST_ONLY if advance_first_only else 0)
-        check(lib().mpcb_closed_loop(self._h, B, steps, dptr(x0), dptr(xs), dptr(ob), int(obs_motion), flags, dptr(xh), dptr(uh),
-                                     iptr(st), iptr(it)), self._h)
+        if aa == 0.0:
+            check(lib().mpcb_closed_loop(self._h, B, steps, dptr(x0), dptr(xs), dptr(ob), int(obs_motion), flags, dptr(xh), dptr(uh),
+                                         iptr(st), iptr(it)), self._h)
+        else:
+            check(lib().mpcb_closed_loop_ref(self._h, B, steps, dptr(x0), dptr(xs), dptr(ob), int(obs_motion), flags, aa, dptr(xh),
+                                             dptr(uh), iptr(st), iptr(it)), self._h)
         return dict(x_hist=xh, u_hist=uh, status=st, iters=it, obs_state=ob)
 
     # ----- scene generation on the device (include/mpcbatch.h, "scene generation") ----------------------------------
@@ -240,16 +258,21 @@ class BatchSolver:
         return DeviceArray(self, shape, dtype)
 
     def solve_device(self, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj=None, d_status=None, d_iters=None, d_kkt=None,
-                     d_lam_g=None, d_lam_x=None, sync=False):
-        """Raw device pointers (ints / c_void_p / DeviceArray).  Asynchronous on the handle's stream unless sync."""
+                     d_lam_g=None, d_lam_x=None, sync=False, d_x_ref=None):
+        """Raw device pointers (ints / c_void_p / DeviceArray).  Asynchronous on the handle's stream unless sync.
+        d_x_ref [B,N,nx]: per-stage reference (mpcb_solve_device_ref)."""
         def p(v):
             if v is None:
                 return None
             if isinstance(v, DeviceArray):
                 return v.ptr
             return C.c_void_p(int(v)) if not isinstance(v, C.c_void_p) else v
-        check(lib().mpcb_solve_device(self._h, B, p(d_x0), p(d_xs), p(d_obs), obs_kind, p(d_z0), p(d_z), p(d_obj), p(d_status),
-                                      p(d_iters), p(d_kkt), p(d_lam_g), p(d_lam_x), 1 if sync else 0), self._h)
+        if d_x_ref is None:
+            check(lib().mpcb_solve_device(self._h, B, p(d_x0), p(d_xs), p(d_obs), obs_kind, p(d_z0), p(d_z), p(d_obj), p(d_status),
+                                          p(d_iters), p(d_kkt), p(d_lam_g), p(d_lam_x), 1 if sync else 0), self._h)
+        else:
+            check(lib().mpcb_solve_device_ref(self._h, B, p(d_x0), p(d_xs), p(d_x_ref), p(d_obs), obs_kind, p(d_z0), p(d_z), p(d_obj),
+                                              p(d_status), p(d_iters), p(d_kkt), p(d_lam_g), p(d_lam_x), 1 if sync else 0), self._h)
 
     # ----- multi-GPU (include/mpcbatch.h, "multi-GPU") ------------------------------------------------------
     def set_devices(self, ids):

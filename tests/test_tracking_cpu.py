@@ -1,0 +1,224 @@
+"""Per-stage reference tracking (mpcb_solve_ref, the TRACK instantiations of mpcb_solve_kin) without a GPU.
+
+The oracle has no tracking cost, so the kernel source is judged by evidence that needs none: with constant rows x_ref[b, i] = c_b the
+tracking NLP IS the oracle's set-point NLP with xs = c_b; with time-varying rows the independent KKT certificate of oracle/kkt_check.py
+(complex-step derivatives) is given the tracking objective through `nlp.xs = x_ref` (KinNlp.f computes X[:-1] - xs).  The kernel
+source is stepped on the CPU by tests/emu_track.  Also here: the C ABI of the new entry points, the drop-in's blend of the window,
+and the machine-code guard of tests/test_kernel_isa.py applied to the mpcb_track_* kernels."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import oracle, kkt_check
+from tests.emu_track import emu_track
+from mpc_motion_planning_amd import scenes, _abi, _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = np.load(os.path.join(os.path.dirname(__file__), "golden", "solutions.npz"))
+NEW_ENTRIES = ("mpcb_solve_ref", "mpcb_solve_device_ref", "mpcb_closed_loop_ref")
+
+
+def product_cfg(N=30, n_obs=1):
+    c = oracle.default_config(N=N, n_obs=n_obs)
+    c.init_rollout = 1; c.mu_init = 10.0; c.second_start = 3; c.start_steer = 0.03        # the settings mpcb_default_config ships
+    return c
+
+
+def lane_change_ref(x0, N=30, T=0.1, y_to=0.0, v=15.0, start=5, length=15):
+    """Stage references of a lane change: x advances at v, y ramps from x0's lane to y_to over `length` stages after `start`."""
+    i = np.arange(N)
+    r = np.zeros((N, 4))
+    r[:, 0] = x0[0] + v * T * (i + 1)
+    r[:, 1] = x0[1] + (y_to - x0[1]) * np.clip((i - start) / length, 0.0, 1.0)
+    r[:, 3] = v
+    return r
+
+
+def speed_profile_ref(x0, N=30, T=0.1, v_from=15.0, v_to=22.0, step_at=10):
+    """Stage references of a speed step at stage `step_at`, in the lane of x0, x following the profile."""
+    v = np.where(np.arange(N) < step_at, v_from, v_to)
+    r = np.zeros((N, 4))
+    r[:, 0] = x0[0] + T * np.cumsum(v)
+    r[:, 1] = 3.5
+    r[:, 3] = v
+    return r
+
+
+def certify(cfg, x0, x_ref, obs, e, integrator="euler"):
+    nlp = kkt_check.KinNlp(cfg.N, cfg.T, x0, np.zeros(4), obs, integrator=integrator)
+    nlp.xs = x_ref                                              # the tracking objective: sum_i (X_i - r_i)' Q (X_i - r_i)
+    c = kkt_check.certificate(nlp, e["z"], e["lam_g"], e["lam_x"])
+    assert c["stationarity"] <= 1e-6 * c["lam_scale"] and c["feas_g"] <= 2e-8 and c["compl"] <= 1e-3 and c["sign"] == 0.0, c
+    assert c["f"] == pytest.approx(e["obj"], rel=1e-10)
+    return c
+
+
+def test_constant_rows_equal_the_set_point_solve_of_the_oracle():
+    """x_ref[b, i] = c_b is the set-point NLP with xs = c_b: same statuses, iterations and trajectories as the oracle."""
+    cfg = product_cfg()
+    xr = np.repeat(G["S_xs"][:, None, :], cfg.N, axis=1)
+    e = emu_track.solve(cfg, G["S_x0"], G["S_xs"], xr, G["S_obs"])
+    assert e["status"][0] == 0 and e["iters"][0] == G["S_iters"][0]
+    assert np.abs(e["z"] - G["S_z"]).max() <= 1e-10
+    B = 16
+    x0, xs, obs = scenes.sample_c2(B, seed=11)
+    rng = np.random.default_rng(5)
+    c = np.stack([rng.uniform(60, 400, B), rng.uniform(0.0, 4.0, B), np.zeros(B), rng.uniform(10, 30, B)], axis=1)
+    xr = np.repeat(c[:, None, :], cfg.N, axis=1)
+    e = emu_track.solve(cfg, x0, xs, xr, obs)                   # the set-point handed to the kernel (xs) is NOT c_b: only x_ref counts
+    r = oracle.solve(cfg, x0, c, obs)
+    assert np.array_equal(e["status"], r["status"]) and np.array_equal(e["iters"], r["iters"])
+    assert (r["status"] == 0).sum() >= B // 2
+    assert np.abs(e["z"] - r["z"]).max() <= 1e-9
+
+
+@pytest.mark.parametrize("n_obs", [0, 1])
+@pytest.mark.parametrize("integrator", ["euler", "rk4"])
+def test_time_varying_references_pass_the_kkt_certificate(n_obs, integrator):
+    """Lane-change and speed-profile references, with the shipped obstacle and without it, keep-out rows, Euler and RK4 shooting rows:
+    solved, and first-order optimal for the tracking objective by the independent certificate."""
+    cfg = product_cfg(30, n_obs)
+    cfg.integrator = _abi.INT_RK4 if integrator == "rk4" else _abi.INT_EULER
+    x0 = G["S_x0"][0]
+    obs = G["S_obs"][:1] if n_obs else None
+    refs = [lane_change_ref(x0, y_to=0.0), speed_profile_ref(x0)]
+    xr = np.stack(refs)
+    e = emu_track.solve(cfg, np.repeat(G["S_x0"], 2, 0), np.repeat(G["S_xs"], 2, 0), xr, None if obs is None else np.repeat(obs, 2, 0))
+    assert (e["status"] == 0).all(), e["status"]
+    for b in range(2):
+        certify(cfg, x0, xr[b], None if obs is None else obs[0], {k: v[b] for k, v in e.items()}, integrator)
+    # the references are followed: the lane change ends in the other lane, the speed step is taken up
+    X = e["z"][:, 2 * cfg.N:].reshape(2, cfg.N + 1, 4)
+    assert X[0, -1, 1] < 1.0 and X[1, -1, 3] > 19.0
+
+
+def test_non_finite_reference_ends_the_instance_with_numeric_status():
+    """A non-finite x_ref entry: MPCB_ST_NUMERIC at iteration 0 for that instance, its neighbour in the batch unaffected."""
+    cfg = product_cfg()
+    x0 = np.repeat(G["S_x0"], 3, 0); xs = np.repeat(G["S_xs"], 3, 0); obs = np.repeat(G["S_obs"], 3, 0)
+    xr = np.repeat(xs[:, None, :], cfg.N, axis=1).copy()
+    xr[0, 7, 1] = np.nan
+    xr[1, cfg.N - 1, 3] = np.inf
+    e = emu_track.solve(cfg, x0, xs, xr, obs)
+    assert list(e["status"][:2]) == [_abi.ST_NUMERIC] * 2 and list(e["iters"][:2]) == [0, 0]
+    assert e["status"][2] == 0 and np.abs(e["z"][2] - G["S_z"][0]).max() <= 1e-10
+
+
+def header_functions():
+    text = open(os.path.join(ROOT, "include", "mpcbatch.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return set(re.findall(r"\b(mpcb_[a-z_]+)\s*\(", text))
+
+
+def test_new_entry_points_in_header_bindings_and_library():
+    names = header_functions()
+    L = _lib.lib()
+    for n in NEW_ENTRIES:
+        assert n in names and n in _lib.SIGNATURES and hasattr(L, n), n
+    assert re.search(r"#define MPCB_ABI_VERSION 3\b", open(os.path.join(ROOT, "include", "mpcbatch.h")).read())
+    assert L.mpcb_version().decode().startswith("mpcbatch 0.4 ")
+    # host-side argument checks that need no device: a NULL handle is refused by every new entry
+    assert L.mpcb_solve_ref(None, 1, None, None, None, None, 0, None, None, None, None, None, None, None, None) == _abi.E_INVALID
+    assert L.mpcb_closed_loop_ref(None, 1, 1, None, None, None, 0, 0, 0.5, None, None, None, None) == _abi.E_INVALID
+
+
+class _StubSolver:
+    """Records every call the drop-in makes on its BatchSolver."""
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+        self.calls = []
+
+    def set_time_grid(self, T_i=None):
+        pass
+
+    def set_bounds(self, *a):
+        pass
+
+    def solve_batch(self, *args, **kw):
+        self.calls.append((args, kw))
+        nz = 2 * self.cfg.N + 4 * (self.cfg.N + 1); ng = 4 * (self.cfg.N + 1) + (self.cfg.N - 1) + self.cfg.n_obs * self.cfg.N
+        return dict(z=np.zeros((1, nz)), obj=np.zeros(1), status=np.zeros(1, np.int32), iters=np.ones(1, np.int32), kkt=np.zeros((1, 4)),
+                    lam_g=np.zeros((1, ng)), lam_x=np.zeros((1, nz)))
+
+
+@pytest.mark.parametrize("module", ["MPC_CBF_optimize_kin", "MPC_CBF_optimize_kin_pre"])
+def test_drop_in_blends_the_window_only_when_aa_is_set(module):
+    import importlib
+    mod = importlib.import_module("mpc_motion_planning_amd." + module)
+    m = mod.MPC_optimize()
+    assert m.aa == 0.0
+    N = m.N_p
+    stub = _StubSolver(m._make_cfg(1))
+    m._batch_solver = lambda cfg: stub
+    x0 = np.array([0, 3, 0, 15.0]); xs = np.array([400, 3.5, 0, 30.0])
+    obs = np.array([[50, 3.5, 0, 8, 4.8, 1.8]])
+    obs_arg = obs if module.endswith("kin") else [np.repeat(obs, N + 1, 0)]
+    ref = np.column_stack([np.arange(N + 1) * 2.0, np.full(N + 1, 3.5), np.zeros(N + 1), np.full(N + 1, 22.0)])
+    p = np.concatenate([x0, xs])
+    z0 = np.zeros(2 * N + 4 * (N + 1))
+    # aa = 0: today's call, argument for argument
+    m.optimize_problem(ego_state=x0, ref_state=ref, **{("obstacle" if module.endswith("kin") else "obs_trajectories"): obs_arg})(x0=z0, p=p)
+    args, kw = stub.calls[-1]
+    assert kw == {"multipliers": True} and len(args) == 4
+    assert np.array_equal(args[0], x0.reshape(1, 4)) and np.array_equal(args[1], xs.reshape(1, 4))
+    assert np.array_equal(args[3], z0.reshape(1, -1))
+    # aa = 0.5: x_ref = 0.5 * ref[1:] + 0.5 * xs
+    m.aa = 0.5
+    m.optimize_problem(ego_state=x0, ref_state=ref, **{("obstacle" if module.endswith("kin") else "obs_trajectories"): obs_arg})(x0=z0, p=p)
+    args, kw = stub.calls[-1]
+    assert set(kw) == {"multipliers", "x_ref"} and kw["x_ref"].shape == (1, N, 4)
+    assert np.array_equal(kw["x_ref"][0], 0.5 * ref[1:] + 0.5 * xs)
+    with pytest.raises(ValueError):
+        m.optimize_problem(ego_state=x0, ref_state=ref[:-1], **{("obstacle" if module.endswith("kin") else "obs_trajectories"): obs_arg})
+
+
+def test_solve_batch_checks_the_reference_shape_before_any_device_call():
+    from mpc_motion_planning_amd.solver import BatchSolver
+    bs = BatchSolver.__new__(BatchSolver)                        # no handle: a shape error must come before the library is called
+    bs.nx, bs.N, bs.nz = 4, 30, 2 * 30 + 4 * 31
+    bs._h = None
+    with pytest.raises(ValueError):
+        bs.solve_batch(np.zeros((2, 4)), np.zeros((2, 4)), x_ref=np.zeros((2, 29, 4)))
+    with pytest.raises(ValueError):
+        bs.solve_batch(np.zeros((2, 4)), np.zeros((2, 4)), x_ref=np.zeros((1, 30, 4)))
+
+
+# ----- machine code of the tracking kernels: the rules of tests/test_kernel_isa.py -------------------------------------------------
+sys.path.insert(0, ROOT)
+from tools import kernel_resources as kr   # noqa: E402
+
+needs_llvm = pytest.mark.skipif(not os.path.exists(os.path.join(kr.LLVM, "llvm-objdump")), reason="ROCm LLVM tools not installed")
+
+
+@pytest.fixture(scope="module")
+def shipped():
+    return kr.kernels()
+
+
+@needs_llvm
+def test_tracking_kernels_mirror_every_kin_instantiation(shipped):
+    ks, non_kernels = shipped
+    assert non_kernels == []
+    kin = sorted(k for k in ks if k.startswith("mpcb_kernel_kin"))
+    trk = sorted(k for k in ks if k.startswith("mpcb_track_kin"))
+    assert len(kin) == 22 and trk == sorted(k.replace("mpcb_kernel_kin", "mpcb_track_kin") for k in kin)
+    assert "mpcb_track_window" in ks
+    for name in trk:
+        k = ks[name]
+        assert k["instr"].get("flat_", 0) == 0, name
+        assert k["instr"].get("s_barrier", 0) == 0, name
+        assert k["wg_max"] == 64 and k["lds_static"] == 0, name
+        twin = ks[name.replace("mpcb_track_kin", "mpcb_kernel_kin")]
+        assert k["scratch"] <= twin["scratch"], "%s: %d B scratch, its untracked twin %d B" % (name, k["scratch"], twin["scratch"])
+
+
+@needs_llvm
+@pytest.mark.parametrize("name", ["mpcb_track_kin<0, false, false>", "mpcb_track_kin<1, false, false>", "mpcb_track_kin<3, false, false>",
+                                  "mpcb_track_kin_resto<0, false, false>", "mpcb_track_kin_resto<1, false, false>"])
+def test_tracking_kernels_of_the_benchmark_scenes_use_no_scratch(shipped, name):
+    k = shipped[0][name]
+    assert k["scratch"] == 0 and k["instr"].get("scratch_", 0) == 0, (name, k["scratch"])
