@@ -290,6 +290,8 @@ struct Solver {
   Opt o;
   int N, nx, na, nw, nobs;
   const double *x0, *xs;
+  const double* xref = nullptr;    // [N][nx] per-stage reference (mpco_solve_ref): row k replaces xs in stage k's cost; NULL: xs everywhere
+  const double* ref(int k) const { return (xref && k < N) ? xref + (size_t)k * nx : xs; }
   ObsP obs[NODES][NOBM];
   bool obs_node[NODES];
   double Tk[NODES];                // step length of stage k: cfg.T, or the time grid (the variable-time grid of kin.py:19-25 made effective)
@@ -435,7 +437,7 @@ struct Solver {
       double gmax = 0;
       for (int k = 0; k < N; ++k) {
         const double* Xk = (k == 0) ? X0guess : X[k];
-        for (int i = 0; i < nx; ++i) gmax = std::max(gmax, std::fabs(2 * c.Q[i] * (Xk[i] - xs[i])));
+        for (int i = 0; i < nx; ++i) gmax = std::max(gmax, std::fabs(2 * c.Q[i] * (Xk[i] - ref(k)[i])));
         for (int i = 0; i < NU; ++i) {
           double gu = 2 * c.R[i] * U[k][i];
           const double* Up = (k == 0) ? c.u_last : U[k - 1];
@@ -524,7 +526,7 @@ struct Solver {
   // ----- evaluation at the current iterate ------------------------------------------------------------------
   void set_main_cost() {                 // kin.py:168-205 / dyn.py:189-225
     for (int k = 0; k <= N; ++k) {
-      for (int i = 0; i < NXM; ++i) { Qc[k][i] = (k < N && i < nx) ? c.Q[i] : 0.0; Xr[k][i] = (i < nx) ? xs[i] : 0.0; }   // no terminal cost
+      for (int i = 0; i < NXM; ++i) { Qc[k][i] = (k < N && i < nx) ? c.Q[i] : 0.0; Xr[k][i] = (i < nx) ? ref(k)[i] : 0.0; }   // no terminal cost
       for (int i = 0; i < NU; ++i) { Rc[k][i] = (k < N) ? c.R[i] : 0.0; Ur[k][i] = 0.0; }
     }
     for (int i = 0; i < NU; ++i) DRc[i] = c.DR[i];
@@ -1237,6 +1239,7 @@ struct Solver {
     status = MPCB_ST_MAXITER;
     for (iters = 0;; ++iters) {
       if (++trips > 3 * c.max_iter + 50) { status = MPCB_ST_RESTO_FAILED; break; }   // phase changes are not iterations: bound them too
+      if (xref && !std::isfinite(fval)) { status = MPCB_ST_NUMERIC; break; }         // a non-finite reference entry: the objective at the start already is (the tracking kernel's check)
       Err e0 = kkt_error(0.0);
       err0 = Emu(e0);
       // IPOPT's OptimalityErrorConvergenceCheck (IpOptErrorConvCheck.cpp): "optimal" = scaled error <= tol AND the unscaled gates
@@ -1313,7 +1316,7 @@ struct Solver {
       for (int k = 1; k <= N; ++k) for (int i = 0; i < nx; ++i) lam_g[dyn_row[k] + i] = -lam[k][i] / os;
       // initial-condition rows: stationarity wrt X_0
       for (int i = 0; i < nx; ++i) {
-        double s = -2 * c.Q[i] * (X[0][i] - xs[i]);
+        double s = -2 * c.Q[i] * (X[0][i] - ref(0)[i]);
         for (int a = 0; a < nx; ++a) s -= me[0].A[a][i] * lam[1][a] / os;
         lam_g[i] = s;
       }
@@ -1410,13 +1413,37 @@ int mpco_model_rhs(const mpcb_config* cfg, const double* x, const double* u, dou
 }
 
 // Oracle batch solve: same arrays as mpcb_solve.  threads <= 0: all OpenMP threads.
+static int solve_batch(const mpcb_config* cfg, int32_t B, const double* x0, const double* xs, const double* xref, const double* obs,
+                       int32_t obs_kind, const double* z0, double* z, double* obj, int32_t* status, int32_t* iters,
+                       double* kkt, double* lam_g, double* lam_x, int32_t threads, const double* tgrid);
+
 int mpco_solve(const mpcb_config* cfg, int32_t B, const double* x0, const double* xs, const double* obs,
                int32_t obs_kind, const double* z0, double* z, double* obj, int32_t* status, int32_t* iters,
                double* kkt, double* lam_g, double* lam_x, int32_t threads, const double* tgrid) {
+  return solve_batch(cfg, B, x0, xs, nullptr, obs, obs_kind, z0, z, obj, status, iters, kkt, lam_g, lam_x, threads, tgrid);
+}
+
+// Oracle tracking solve (mpcb_solve_ref): x_ref [B][N][nx], row k replaces xs in stage k's cost (the main phase's Xr, the objective
+// scaling at the start, the multipliers of the pinned X_0 rows).  Kinematic model only, as the library.  A non-finite x_ref entry
+// ends its instance with MPCB_ST_NUMERIC at iteration 0, and no second attempt follows.
+int mpco_solve_ref(const mpcb_config* cfg, int32_t B, const double* x0, const double* xs, const double* x_ref, const double* obs,
+                   int32_t obs_kind, const double* z0, double* z, double* obj, int32_t* status, int32_t* iters,
+                   double* kkt, double* lam_g, double* lam_x, int32_t threads, const double* tgrid) {
+  int rc = check_cfg(cfg);
+  if (rc != MPCB_OK) return rc;
+  if (!x_ref) return MPCB_E_INVALID;
+  if (cfg->model != MPCB_MODEL_KIN) return MPCB_E_UNSUPPORTED;
+  return solve_batch(cfg, B, x0, xs, x_ref, obs, obs_kind, z0, z, obj, status, iters, kkt, lam_g, lam_x, threads, tgrid);
+}
+
+static int solve_batch(const mpcb_config* cfg, int32_t B, const double* x0, const double* xs, const double* xref, const double* obs,
+                       int32_t obs_kind, const double* z0, double* z, double* obj, int32_t* status, int32_t* iters,
+                       double* kkt, double* lam_g, double* lam_x, int32_t threads, const double* tgrid) {
   int rc = check_cfg(cfg);
   if (rc != MPCB_OK) return rc;
   if (B < 0 || !x0 || !xs || !z || (cfg->n_obs > 0 && !obs)) return MPCB_E_INVALID;
   int nx, nz, ng; mpco_dims(cfg, &nx, &nz, &ng);
+  const size_t xr_stride = (size_t)cfg->N * nx;
   const size_t obs_stride = (size_t)cfg->n_obs * 6 * (obs_kind == MPCB_OBSIN_PREDICTED ? cfg->N + 1 : 1);
 #ifdef _OPENMP
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads > 0 ? threads : omp_get_max_threads())
@@ -1427,6 +1454,8 @@ int mpco_solve(const mpcb_config* cfg, int32_t B, const double* x0, const double
     static thread_local void* arena = nullptr;
     if (!arena) arena = ::operator new(sizeof(Solver));
     Solver* s = new (arena) Solver(*cfg);
+    const double* xr = xref ? xref + (size_t)b * xr_stride : nullptr;
+    s->xref = xr;
     // cfg.second_start = 3: a cold start (z0 = NULL) behaves as 1, a solve with a start vector as 2
     const int ss = cfg->second_start == 3 ? (z0 ? 2 : 1) : cfg->second_start;
     s->defer_restoration = ss == 1 && cfg->init_rollout != 0;
@@ -1437,10 +1466,12 @@ int mpco_solve(const mpcb_config* cfg, int32_t B, const double* x0, const double
     // second attempt from z = 0 with a fresh solver state, as the HIP library's second-start passes
     bool fin = true;                                  // non-finite inputs: the first attempt's verdict (at iteration 0) stands
     for (int i = 0; i < nx; ++i) fin = fin && std::isfinite(x0[(size_t)b * nx + i]) && std::isfinite(xs[(size_t)b * nx + i]);
+    if (xr) for (size_t i = 0; i < xr_stride; ++i) fin = fin && std::isfinite(xr[i]);     // ... and of the per-stage reference
     if (ok && fin && cfg->second_start && cfg->init_rollout && s->status != MPCB_ST_SOLVED && s->status != MPCB_ST_ACCEPTABLE) {
       const int it0 = s->iters;
       s->~Solver();
       s = new (arena) Solver(*cfg);
+      s->xref = xr;
       ok = s->init(x0 + (size_t)b * nx, xs + (size_t)b * nx, obs ? obs + b * obs_stride : nullptr, obs_kind, nullptr, tgrid, true);
       if (ok) s->solve(); else s->eval_point();
       s->iters_prev = it0;

@@ -31,6 +31,7 @@ def lib():
     if _LIB is None:
         _LIB = C.CDLL(build())
         _LIB.mpco_solve.restype = C.c_int
+        _LIB.mpco_solve_ref.restype = C.c_int
         _LIB.mpco_default_config.restype = C.c_int
         _LIB.mpco_dims.restype = C.c_int
     return _LIB
@@ -70,8 +71,10 @@ def dims(cfg):
     return nx.value, nz.value, ng.value
 
 
-def solve(cfg, x0, xs, obs=None, z0=None, threads=0, want_multipliers=True, tgrid=None):
-    """Returns dict(z, obj, status, iters, kkt, lam_g, lam_x); arrays are [B, ...]."""
+def solve(cfg, x0, xs, obs=None, z0=None, threads=0, want_multipliers=True, tgrid=None, x_ref=None):
+    """Returns dict(z, obj, status, iters, kkt, lam_g, lam_x); arrays are [B, ...].
+    x_ref [B,N,nx] | None: per-stage reference, row i replaces xs in stage i's cost (mpco_solve_ref, the tracking solve of
+    mpcb_solve_ref; kinematic model only).  None is mpco_solve."""
     x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
     xs = np.ascontiguousarray(np.atleast_2d(xs), dtype=np.float64)
     B = x0.shape[0]
@@ -97,11 +100,18 @@ def solve(cfg, x0, xs, obs=None, z0=None, threads=0, want_multipliers=True, tgri
     kkt = np.zeros((B, 4))
     lam_g = np.zeros((B, ng)) if want_multipliers else None
     lam_x = np.zeros((B, nz)) if want_multipliers else None
-    rc = lib().mpco_solve(C.byref(cfg), C.c_int32(B), dptr(x0), dptr(xs), dptr(obs), C.c_int32(kind), dptr(z0),
-                          dptr(z), dptr(obj), iptr(st), iptr(it), dptr(kkt), dptr(lam_g), dptr(lam_x),
-                          C.c_int32(threads), dptr(tg))
+    if x_ref is None:
+        rc = lib().mpco_solve(C.byref(cfg), C.c_int32(B), dptr(x0), dptr(xs), dptr(obs), C.c_int32(kind), dptr(z0),
+                              dptr(z), dptr(obj), iptr(st), iptr(it), dptr(kkt), dptr(lam_g), dptr(lam_x),
+                              C.c_int32(threads), dptr(tg))
+    else:
+        x_ref = np.ascontiguousarray(x_ref, dtype=np.float64)
+        assert x_ref.shape == (B, cfg.N, nx), "x_ref must be [B,N,nx] = [%d,%d,%d], got %s" % (B, cfg.N, nx, x_ref.shape)
+        rc = lib().mpco_solve_ref(C.byref(cfg), C.c_int32(B), dptr(x0), dptr(xs), dptr(x_ref), dptr(obs), C.c_int32(kind),
+                                  dptr(z0), dptr(z), dptr(obj), iptr(st), iptr(it), dptr(kkt), dptr(lam_g), dptr(lam_x),
+                                  C.c_int32(threads), dptr(tg))
     if rc != 0:
-        raise RuntimeError("mpco_solve failed with code %d" % rc)
+        raise RuntimeError("%s failed with code %d" % ("mpco_solve" if x_ref is None else "mpco_solve_ref", rc))
     return dict(z=z, obj=obj, status=st, iters=it, kkt=kkt, lam_g=lam_g, lam_x=lam_x)
 
 
