@@ -1,0 +1,176 @@
+"""Non-default problem data and solver options without a GPU: every case of tests/config_cases.py through the kernel source stepped
+on the CPU (tests/emu, tests/emu_track for the tracking case) against the oracle, and through the independent certificate of
+oracle/kkt_check.py built from the config alone (KinNlp.from_config / DynNlp.from_config).  The device tier of the same table is
+tests/test_config_gpu.py."""
+import numpy as np
+import pytest
+
+from oracle import oracle, kkt_check
+from tests import config_cases as cc
+from tests.emu import emu
+from tests.emu_track import emu_track
+from mpc_motion_planning_amd import scenes, _abi
+
+
+def _random_points(nlp, rng, n=3):
+    for _ in range(n):
+        z = rng.normal(size=nlp.nz)
+        if nlp.nz == 2 * nlp.N + 6 * (nlp.N + 1):                    # dynamic model: vx away from 0 (the tyre model divides by it) and
+            X = z[2 * nlp.N:].reshape(nlp.N + 1, 6)                  # every node outside the ellipses (the row is sqrt(h))
+            X[:, 3] = rng.uniform(5, 20, nlp.N + 1); X[:, 1] += 40.0
+        yield z
+
+
+def test_from_config_of_the_default_config_is_the_plain_constructor():
+    """from_config(default cfg) states the NLP the existing constructors state: same f, g and bounds, bit for bit, at random points."""
+    rng = np.random.default_rng(7)
+    x0, xs, obs = scenes.sample_c2(2, seed=3)
+    _, _, _, traj = scenes.sample_c3(2, N=30, dt=0.1, seed=5)
+    for ob, n_obs, mode, gamma, integ in ((obs[0], 1, _abi.OBS_KEEPOUT, 1.0, _abi.INT_EULER), (traj[0], 3, _abi.OBS_DCBF, 0.5, _abi.INT_EULER),
+                                          (None, 0, _abi.OBS_KEEPOUT, 1.0, _abi.INT_RK4)):
+        cfg = oracle.default_config(N=30, n_obs=n_obs); cfg.obs_mode = mode; cfg.gamma = gamma; cfg.integrator = integ
+        a = kkt_check.KinNlp(30, 0.1, x0[0], xs[0], ob, obs_mode="dcbf" if mode == _abi.OBS_DCBF else "keepout", gamma=gamma,
+                             integrator="rk4" if integ == _abi.INT_RK4 else "euler")
+        b = kkt_check.KinNlp.from_config(cfg, x0[0], xs[0], ob)
+        assert (a.nz, a.ng) == (b.nz, b.ng)
+        for k in ("lbx", "ubx", "lbg", "ubg"):
+            assert np.array_equal(getattr(a, k), getattr(b, k)), k
+        for z in _random_points(a, rng):
+            assert a.f(z) == b.f(z) and np.array_equal(a.g(z), b.g(z))
+    d0, ds, dobs = scenes.sample_c4(2, seed=9, n_obs=3)
+    for n_obs in (1, 3):
+        cfg = oracle.default_config(model=_abi.MODEL_DYN, N=20, n_obs=n_obs)
+        a = kkt_check.DynNlp(20, 0.1, d0[0], ds[0], dobs[0, :n_obs])
+        b = kkt_check.DynNlp.from_config(cfg, d0[0], ds[0], dobs[0, :n_obs])
+        assert (a.nz, a.ng) == (b.nz, b.ng) == (2 * 20 + 6 * 21, 6 * 21 + 2 * 19 + 21 * n_obs)
+        for k in ("lbx", "ubx", "lbg", "ubg"):
+            assert np.array_equal(getattr(a, k), getattr(b, k)), k
+        for z in _random_points(a, rng):
+            assert a.f(z) == b.f(z) and np.array_equal(a.g(z), b.g(z))
+            lam = rng.normal(size=a.ng)
+            assert np.array_equal(a.convert_obstacle_multipliers(z, lam), b.convert_obstacle_multipliers(z, lam))
+
+
+def test_from_config_follows_the_config():
+    """Row counts, row order and bounds of from_config against the layout include/mpcbatch.h documents, for the structures the default
+    never reaches: no rate rows, one-sided boxes, terminal rows, block and interleaved rate rows of one or both controls."""
+    x0, xs, obs = scenes.sample_c2(1, seed=3)
+    N = 30
+    cfg = cc.oracle_cfg(cc.BY_NAME["no_y_box_no_rate_rows"], oracle)
+    n = kkt_check.KinNlp.from_config(cfg, x0[0], xs[0], obs[0])
+    assert n.ng == oracle.dims(cfg)[2] == 4 * (N + 1) + N and np.all(np.isinf(n.lbx[2 * N + 1::4])) and np.all(np.isinf(n.ubx[2 * N + 1::4]))
+    cfg = cc.oracle_cfg(cc.BY_NAME["bounds"], oracle)
+    n = kkt_check.KinNlp.from_config(cfg, x0[0], xs[0], obs[0])
+    assert n.ng == oracle.dims(cfg)[2] and np.all(n.lbg[4 * (N + 1):4 * (N + 1) + N - 1] == -0.006) and np.all(n.ubg[4 * (N + 1):4 * (N + 1) + N - 1] == 0.011)
+    assert list(n.lbx[:2]) == [-0.3, -2.0] and list(n.ubx[:2]) == [0.5, 1.2] and list(n.lbx[2 * N:2 * N + 4]) == [-np.inf, -0.5, -np.inf, 0.0]
+    assert list(n.ubx[-4:]) == [np.inf, 6.0, np.inf, 33.0]
+    cfg = cc.oracle_cfg(cc.BY_NAME["terminal_rows_geometry"], oracle)
+    n = kkt_check.KinNlp.from_config(cfg, x0[0], xs[0], obs[0])
+    assert n.ng == oracle.dims(cfg)[2] == 4 * (N + 1) + (N - 1) + (N + 1)
+    assert n.sx[0, 0] == 2.0 + 4.8 / 2 + 0.6 and n.sy[0, 0] == 1.1 + 1.8 / 2 + 0.8
+    cfg = cc.oracle_cfg(cc.BY_NAME["T_0.15"], oracle)
+    n = kkt_check.KinNlp.from_config(cfg, x0[0], xs[0], obs[0])
+    assert n.T == 0.15 and n.ubg[4 * (N + 1)] == pytest.approx(5 * np.pi / 180 * 0.15, rel=1e-15)
+    # dynamic model: interleaved rows of both controls, of the acceleration alone, and the same as one block (stage-major)
+    d0, ds, dobs = scenes.sample_c4(1, seed=9, n_obs=1)
+    cfg = cc.oracle_cfg(cc.BY_NAME["dyn_bounds"], oracle)
+    n = kkt_check.DynNlp.from_config(cfg, d0[0], ds[0], dobs[0])
+    assert n.ng == oracle.dims(cfg)[2] and list(n.lbg[12 + 6:12 + 6 + 2]) == [cfg.du_lo[0], -0.2] and list(n.ubg[12 + 6:12 + 6 + 2]) == [cfg.du_hi[0], 0.1]
+    assert n.sx[0, 0] == 5.0 and n.sy[0, 0] == 1.4 and list(n.lbx[2 * 20:2 * 20 + 6]) == [-np.inf, -1.0, -np.inf, 0.0, -2.0, -np.inf]
+    one = cfg.copy(); one.du_lo[0], one.du_hi[0] = -np.inf, np.inf
+    n1 = kkt_check.DynNlp.from_config(one, d0[0], ds[0], dobs[0])
+    assert n1.ng == oracle.dims(one)[2] == n.ng - 19 and n1.rate_cols == [1] and n1.lbg[12 + 6] == -0.2 and n1.lbg[12 + 7] == 0.0
+    blk = cfg.copy(); blk.rate_interleaved = 0
+    nb = kkt_check.DynNlp.from_config(blk, d0[0], ds[0], dobs[0])
+    z = next(_random_points(n, np.random.default_rng(1)))
+    gi, gb = n.g(z), nb.g(z)
+    assert nb.ng == n.ng and np.array_equal(gb[6 * 21:6 * 21 + 2], gi[12 + 6:12 + 8]) and np.array_equal(gb[6:12], gi[6:12]) and np.array_equal(gb[12:18], gi[12:18])
+    assert np.array_equal(np.sort(gi), np.sort(gb))
+    assert n._pattern_key() != nb._pattern_key() != n1._pattern_key()
+
+
+@pytest.mark.parametrize("name", ["default", "no_y_box_no_rate_rows", "terminal_rows_geometry", "gen_mixed", "dyn_bounds"])
+def test_coloured_jacobian_equals_the_dense_one(name):
+    """jac_g (columns that share no row perturbed together, pattern cached per structure) against jac_g_dense (one complex step per
+    variable) on structures that differ in row count only — the cache must keep them apart — and on one with terminal rows."""
+    case = cc.BY_NAME[name]
+    cfg = cc.oracle_cfg(case, oracle)
+    x0, xs, obs, _ = cc.scenes(case, 2)
+    rng = np.random.default_rng(3)
+    for b in range(2):
+        nlp = cc.nlp_of(case, cfg, x0, xs, obs, None, b)
+        for z in _random_points(nlp, rng, 2):
+            J, D = nlp.jac_g(z), nlp.jac_g_dense(z)
+            assert J.shape == D.shape == (nlp.ng, nlp.nz) and np.array_equal(J, D)
+    if name == "no_y_box_no_rate_rows":                           # the default structure right after it: another cache entry
+        dflt = kkt_check.KinNlp.from_config(cc.oracle_cfg(cc.BY_NAME["default"], oracle), x0[0], xs[0], obs[0])
+        z = rng.normal(size=dflt.nz)
+        assert dflt.ng == nlp.ng + 29 and np.array_equal(dflt.jac_g(z), dflt.jac_g_dense(z))
+
+
+def test_oracle_solves_enough_of_every_gpu_batch():
+    """The condition under which a case may be in the table: the CPU oracle alone solves >= 0.95 of the batch the GPU tier runs
+    (status cases: ends as the case expects)."""
+    for case in cc.CASES:
+        cfg = cc.oracle_cfg(case, oracle)
+        x0, xs, obs, xr = cc.scenes(case)
+        r = oracle.solve(cfg, x0, xs, obs, x_ref=xr, want_multipliers=False)
+        want = _abi.ST_SOLVED if case.expect is None else case.expect
+        frac = (r["status"] == want).mean()
+        print("%-26s oracle alone: status %d on %.4f of %d" % (case.name, want, frac, len(x0)))
+        assert len(x0) == cc.GPU_BATCH and frac >= 0.95, (case.name, frac)
+
+
+def _step_kernel_source(case, cfg, x0, xs, obs, xr):
+    if case.track:
+        return emu_track.solve(cfg, x0, xs, xr, obs)
+    return emu.solve(cfg, x0, xs, obs)
+
+
+def _cpu_instances(case, cfg):
+    """The first CPU_BATCH scenes of the case's GPU batch that the oracle ends as the case expects, and the oracle's results on them."""
+    x0, xs, obs, xr = cc.scenes(case)
+    r = oracle.solve(cfg, x0, xs, obs, x_ref=xr)
+    want = _abi.ST_SOLVED if case.expect is None else case.expect
+    idx = np.nonzero(r["status"] == want)[0][:cc.CPU_BATCH[case.model]]
+    assert len(idx) == cc.CPU_BATCH[case.model]
+    return x0[idx], xs[idx], obs[idx], (None if xr is None else xr[idx]), {k: (v[idx] if v is not None else None) for k, v in r.items()}
+
+
+@pytest.mark.parametrize("case", cc.SOLVE_CASES, ids=cc.ids(cc.SOLVE_CASES))
+def test_kernel_source_against_oracle_and_certificate(case):
+    """Status, iteration count, trajectory and multipliers of the stepped kernel source against the oracle, and the from_config
+    certificate on three instances, with the kernel's own objective against the certificate's f."""
+    cfg = cc.oracle_cfg(case, oracle)
+    x0, xs, obs, xr, r = _cpu_instances(case, cfg)
+    e = _step_kernel_source(case, cfg, x0, xs, obs, xr)
+    dz = np.abs(e["z"] - r["z"]).max()
+    dg = (np.abs(e["lam_g"] - r["lam_g"]).max(axis=1) / np.maximum(1.0, np.abs(r["lam_g"]).max(axis=1))).max()
+    dx = (np.abs(e["lam_x"] - r["lam_x"]).max(axis=1) / np.maximum(1.0, np.abs(r["lam_x"]).max(axis=1))).max()
+    print("%-26s status %s iters emu %s oracle %s  L-inf(z) %.2e  lam_g %.2e  lam_x %.2e"
+          % (case.name, e["status"].tolist(), e["iters"].tolist(), r["iters"].tolist(), dz, dg, dx))
+    assert np.array_equal(e["status"], r["status"]) and (r["status"] == 0).all()
+    assert (e["iters"] != r["iters"]).sum() <= 1
+    assert dz <= 1e-8 and dg <= 1e-6 and dx <= 1e-6
+    assert np.abs(e["obj"] / r["obj"] - 1).max() <= 1e-9
+    for b in range(3):
+        cc.certify(case, cfg, x0, xs, obs, xr, e, b)
+    # the case is not the default problem in disguise: its solution differs from the default config's on the same scenes
+    if (case.edit is not None and case.name != "scaling") or case.T != 0.1:             # (`scaling` changes solver options only)
+        d = oracle.solve(cc.product(oracle.default_config(model=case.model, N=case.N, T=0.1, n_obs=case.n_obs)), x0, xs, obs, want_multipliers=False)
+        both = d["status"] == 0
+        assert both.any() and np.abs(d["z"][both] - r["z"][both]).max() > 1e-4
+
+
+@pytest.mark.parametrize("case", cc.STATUS_CASES, ids=cc.ids(cc.STATUS_CASES))
+def test_kernel_source_ends_with_the_status_the_options_ask_for(case):
+    cfg = cc.oracle_cfg(case, oracle)
+    x0, xs, obs, xr, r = _cpu_instances(case, cfg)
+    e = _step_kernel_source(case, cfg, x0, xs, obs, xr)
+    print("%-26s status %s iters emu %s oracle %s" % (case.name, e["status"].tolist(), e["iters"].tolist(), r["iters"].tolist()))
+    assert (e["status"] == case.expect).all() and (r["status"] == case.expect).all()
+    if case.expect == _abi.ST_MAXITER:
+        assert (e["iters"] == 12).all() and (r["iters"] == 12).all()
+    else:
+        assert np.array_equal(e["iters"], r["iters"])
+        assert np.abs(e["z"] - r["z"]).max() <= 1e-8

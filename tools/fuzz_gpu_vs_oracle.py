@@ -1,6 +1,9 @@
 """Differential fuzz: random NLP structures (model, horizon, obstacle count / kind / row form, tolerance, start) solved by the
 HIP library and by the CPU oracle; reports every disagreement.  Run on a GPU box:
-    python tools/fuzz_gpu_vs_oracle.py [cases] [seed]
+    python tools/fuzz_gpu_vs_oracle.py [cases] [seed] [data]
+With `data` (perturb_data=True) the problem data is random as well: weights, boxes, rate bounds, geometry and vehicle / tyre
+parameters within about +-40 % of the defaults, u_last and du0_cost; drawn from a second generator, so the structures of a seed
+are the same with and without it.
 Exit code 1 if any case disagrees beyond the test-suite tolerances (tests/test_gpu_parity.py, which also runs a short
 fixed-seed pass of `run`)."""
 import sys
@@ -13,7 +16,34 @@ from mpc_motion_planning_amd.solver import BatchSolver, default_config          
 from oracle import oracle                                                         # noqa: E402
 
 
-def one_case(rng, c):
+def perturb(cfg, rng2):
+    """Problem data within about +-40 % of the defaults (the ellipse at most 15 % larger: the samplers keep x0 out of the default one)."""
+    def u(lo=0.6, hi=1.4):
+        return float(rng2.uniform(lo, hi))
+    nx = cfg.nx()
+    for i in range(nx):
+        cfg.Q[i] *= u()
+    for i in range(2):
+        cfg.R[i] *= u(); cfg.DR[i] *= u(); cfg.u_lo[i] *= u(); cfg.u_hi[i] *= u()
+        if np.isfinite(cfg.du_lo[i]):
+            cfg.du_lo[i] *= u()
+        if np.isfinite(cfg.du_hi[i]):
+            cfg.du_hi[i] *= u()
+    cfg.u_last[0] = float(rng2.uniform(-0.05, 0.05)); cfg.u_last[1] = float(rng2.uniform(-1.0, 1.0))
+    if rng2.random() < 0.3:
+        cfg.du0_cost = 1 - cfg.du0_cost
+    cfg.x_lo[1] *= u(); cfg.x_hi[1] *= u(0.92, 1.4)               # the scenes start at y in [-0.5, 4.5]
+    cfg.x_hi[3] *= u(0.7, 1.4)
+    if nx == 6:
+        cfg.x_lo[4] *= u(); cfg.x_hi[4] *= u()
+        for k in ("veh_m", "veh_lf", "veh_lr", "veh_Iz", "aopt_f", "aopt_r", "Fymax_f", "Fymax_r"):
+            setattr(cfg, k, getattr(cfg, k) * u())
+    cfg.veh_l *= u()
+    for k in ("ego_hl", "ego_hw", "safe_disl", "safe_disw", "obs_sx_fixed", "obs_sy_fixed"):
+        setattr(cfg, k, getattr(cfg, k) * u(0.6, 1.15))
+
+
+def one_case(rng, c, rng2=None):
     dyn = rng.random() < 0.35
     N = int(rng.choice([1, 2, 3, 5, 8, 13, 20, 30, 31, 32, 33, 40, 50, 62, 63]))
     n_obs = int(rng.choice([0, 1, 1, 2, 3, 3, 4, 5, 8]))
@@ -44,6 +74,10 @@ def one_case(rng, c):
         cfg.init_rollout = 0                     # model): both solvers fail there, in different ways
     desc = "case %d: %s N=%d n_obs=%d(%s) B=%d mode=%d gamma=%.2f term=%d tol=%g rollout=%d" % (
         c, "dyn" if dyn else "kin", N, n_obs, kind, B, cfg.obs_mode, cfg.gamma, cfg.obs_terminal, cfg.tol, cfg.init_rollout)
+    if rng2 is not None:
+        perturb(cfg, rng2)
+        desc += " data: veh_l=%.2f Q1=%.3g R0=%.3g u_hi=(%.3f,%.2f) y=[%.2f,%.2f] du0_cost=%d" % (
+            cfg.veh_l, cfg.Q[1], cfg.R[0], cfg.u_hi[0], cfg.u_hi[1], cfg.x_lo[1], cfg.x_hi[1], cfg.du0_cost)
     import os
     if os.environ.get("MPCB_FUZZ_VERBOSE"):
         print("  starting " + desc, flush=True)
@@ -68,11 +102,12 @@ def one_case(rng, c):
     return ok, desc + " -> status agreement %.2f, solved %d/%d, solved on one side only %d, L-inf(z) %.2e, other basin %d%s" % (same, int(both.sum()), B, flips, err, far, "" if ok else "  <-- MISMATCH")
 
 
-def run(cases=60, seed=0, verbose=True):
+def run(cases=60, seed=0, verbose=True, perturb_data=False):
     rng = np.random.default_rng(seed)
+    rng2 = np.random.default_rng([seed, 1]) if perturb_data else None       # a generator of its own: rng's sequence does not depend on it
     bad = 0
     for c in range(cases):
-        ok, line = one_case(rng, c)
+        ok, line = one_case(rng, c, rng2)
         if verbose or not ok:
             print(line)
         bad += 0 if ok else 1
@@ -82,4 +117,5 @@ def run(cases=60, seed=0, verbose=True):
 
 
 if __name__ == "__main__":
-    sys.exit(1 if run(int(sys.argv[1]) if len(sys.argv) > 1 else 60, int(sys.argv[2]) if len(sys.argv) > 2 else 0) else 0)
+    sys.exit(1 if run(int(sys.argv[1]) if len(sys.argv) > 1 else 60, int(sys.argv[2]) if len(sys.argv) > 2 else 0,
+                      perturb_data=len(sys.argv) > 3 and sys.argv[3] == "data") else 0)
