@@ -287,6 +287,56 @@ int mpcb_closed_loop_ref(mpcb_handle* h, int32_t B, int32_t steps,
                          const double* x0, const double* xs, double* obs_state, int32_t obs_motion, int32_t flags, double aa,
                          double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist);
 
+/* ---- per-instance problem data: heterogeneous batches in one launch ------------------------------------------------------------
+ * Everything in mpcb_config belongs to the handle; these entries let the DATA of the config differ between the instances of one batch
+ * (a sweep over cost weights or safety margins, a robustness study over vehicle and tyre constants, a mixed fleet), so that B tunings
+ * are one full launch instead of B one-wave launches.
+ *   mpcb_params_create   cfgs[b] is the config mpcb_create would have been given for instance b.  All B rows are validated on the
+ *                        host and uploaded: the result is an opaque, read-only, device-resident set that many solves can reuse and
+ *                        that solves in flight together (mpcb_set_inflight) may share.  A row is accepted when it passes the checks
+ *                        of mpcb_create AND is structurally equal to the handle's current config (after mpcb_set_bounds):
+ *                        struct_size, every int32_t field (model, N, n_obs, obs_mode, obs_terminal, du0_cost, rate_interleaved,
+ *                        max_iter, mu_strategy, init_rollout, integrator, restoration, acceptable_iter, second_start), T, gamma, and
+ *                        which entries of u_lo / u_hi / x_lo / x_hi / du_lo / du_hi are bounds as the kernels decide it (a lower one
+ *                        > -1e300, an upper one < 1e300): the row pattern, ng and the layout of lam_g.  Every other double may differ per instance: Q, R, DR, u_last, the values of the boxes and rate
+ *                        bounds, obs_hmin, ego_hl / ego_hw, safe_dis*, obs_s*_fixed, veh_l, the dyn vehicle and tyre constants, the
+ *                        interior-point options and tolerances, start_steer.
+ *                        A row that fails: MPCB_E_INVALID, its index in *first_bad (may be NULL; -1 when no row is at fault), the
+ *                        field named by mpcb_last_error.
+ *   mpcb_params_check    the same validation against `base` in place of a handle's config, on the host alone (no device, no handle;
+ *                        the message goes where mpcb_create's goes: mpcb_last_error(NULL)).
+ *   mpcb_params_destroy  waits for the handle's lanes and its stream, then frees the set.  Sets still alive at mpcb_destroy are freed there.
+ *   mpcb_solve_params / mpcb_solve_device_params / mpcb_closed_loop_params
+ *                        mpcb_solve / mpcb_solve_device / mpcb_closed_loop with instance b solved under row b (in the closed loop the
+ *                        plant step x0 <- x0 + T f(x0, U_0) as well: wheelbase, vehicle and tyre constants of row b).  B must equal
+ *                        the set's B and p must be a live set of h: MPCB_E_INVALID otherwise.  mpcb_solve_device_params is lane-aware
+ *                        like mpcb_solve_device; results do not depend on mpcb_set_inflight.  A set whose rows all equal the handle's
+ *                        config returns bit for bit what the plain entries return, and a mixed batch what one handle per distinct
+ *                        config returns on its instances.
+ * Supported: the kinematic model with keep-out or gamma = 1 rows and the dynamic model, MPCB_INT_EULER, n_obs <= 3, single-device
+ * handles.  General gamma, MPCB_INT_RK4, n_obs > 3, a device group (mpcb_set_devices) and a time grid (mpcb_set_time_grid) return
+ * MPCB_E_UNSUPPORTED; there is no per-stage reference (mpcb_solve_ref) with a set.  Per-instance STRUCTURE (N, n_obs, modes, T) needs
+ * one handle per structure, as before. */
+typedef struct mpcb_params mpcb_params;
+int mpcb_params_check(const mpcb_config* base, const mpcb_config* cfgs, int32_t B, int32_t* first_bad);
+int mpcb_params_create(mpcb_handle* h, const mpcb_config* cfgs, int32_t B, mpcb_params** out, int32_t* first_bad);
+int mpcb_params_destroy(mpcb_handle* h, mpcb_params* p);
+int mpcb_solve_params(mpcb_handle* h, int32_t B, const mpcb_params* p,
+                      const double* x0, const double* xs,
+                      const double* obs, int32_t obs_kind,
+                      const double* z0,
+                      double* z, double* obj, int32_t* status, int32_t* iters, double* kkt,
+                      double* lam_g, double* lam_x);
+int mpcb_solve_device_params(mpcb_handle* h, int32_t B, const mpcb_params* p,
+                             const double* d_x0, const double* d_xs,
+                             const double* d_obs, int32_t obs_kind,
+                             const double* d_z0,
+                             double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt,
+                             double* d_lam_g, double* d_lam_x, int32_t sync);
+int mpcb_closed_loop_params(mpcb_handle* h, int32_t B, int32_t steps, const mpcb_params* p,
+                            const double* x0, const double* xs, double* obs_state, int32_t obs_motion, int32_t flags,
+                            double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist);
+
 /* ---- scene generation on the device -----------------------------------------------------------------------
  * Counter-based random scenes (Philox4x32-10 keyed by `seed`, counter = global scene index): scene i is the same whichever GPU,
  * batch or chunk it is generated in, so 8 GPUs draw disjoint slices of one Monte-Carlo population from (seed, first_index).

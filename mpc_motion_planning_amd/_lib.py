@@ -36,6 +36,13 @@ SIGNATURES = {
     "mpcb_solve_trace": (C.c_int, [_H, _PD, _PD, _PD, C.c_int32, _PD, _PD, _PI, _PI, _PD]),
     "mpcb_closed_loop": (C.c_int, [_H, C.c_int32, C.c_int32, _PD, _PD, _PD, C.c_int32, C.c_int32, _PD, _PD, _PI, _PI]),
     "mpcb_closed_loop_ref": (C.c_int, [_H, C.c_int32, C.c_int32, _PD, _PD, _PD, C.c_int32, C.c_int32, C.c_double, _PD, _PD, _PI, _PI]),
+    "mpcb_params_check": (C.c_int, [C.POINTER(MpcbConfig), C.POINTER(MpcbConfig), C.c_int32, _PI]),
+    "mpcb_params_create": (C.c_int, [_H, C.POINTER(MpcbConfig), C.c_int32, C.POINTER(C.c_void_p), _PI]),
+    "mpcb_params_destroy": (C.c_int, [_H, C.c_void_p]),
+    "mpcb_solve_params": (C.c_int, [_H, C.c_int32, C.c_void_p, _PD, _PD, _PD, C.c_int32, _PD, _PD, _PD, _PI, _PI, _PD, _PD, _PD]),
+    "mpcb_solve_device_params": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "mpcb_closed_loop_params": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, _PD, _PD, _PD, C.c_int32, C.c_int32, _PD, _PD, _PI, _PI]),
     "mpcb_sample_scenes": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpcb_closed_loop_sampled": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PI, _PI]),
     "mpcb_predict_obstacles": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, _PD, _PD]),

@@ -120,6 +120,54 @@ __global__ __launch_bounds__(64, 1) void mpcb_kernel_dyn_resto(const MpcbKArgs a
   mpcb_solve_dyn<NOBS, true>(a, (int)blockIdx.x, mpcb_lds, MPCB_PASS_RESTO);
 }
 
+// per-instance problem data (mpcb_solve_params, a.cfgs != NULL): the PARAMS instantiations of the two solves, every config read from row
+// blockIdx.x of the parameter set.  Euler, keep-out / gamma = 1 rows, up to 3 obstacles; the fused second attempt follows the rule of the
+// twins (the structural integers mpcb_second_kind1 reads are equal in a.cfg and in every row).  Ten instantiations, the deliberate cap:
+// the library is one translation unit and every instantiation costs build time.
+template <int NOBS>
+__global__ __launch_bounds__(64, MPCB_WAVES_PER_SIMD) void mpcb_param_kin(const MpcbKArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
+  if constexpr (mpcb_kin_fuses<NOBS, false, false>) {
+    int pass = a.pass;
+#pragma clang loop unroll(disable)
+    for (;;) {
+      mpcb_solve_kin<NOBS, false, false, false, false, true>(a, (int)blockIdx.x, mpcb_lds, pass);
+      if (!mpcb_second_attempt_here(a, (int)blockIdx.x, pass)) break;
+      pass = MPCB_PASS_SECOND;
+    }
+  } else {
+    mpcb_solve_kin<NOBS, false, false, false, false, true>(a, (int)blockIdx.x, mpcb_lds, a.pass);
+  }
+}
+
+template <int NOBS>
+__global__ __launch_bounds__(64, 1) void mpcb_param_kin_resto(const MpcbKArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
+  mpcb_solve_kin<NOBS, false, true, false, false, true>(a, (int)blockIdx.x, mpcb_lds, MPCB_PASS_RESTO);
+}
+
+template <int NOBS>
+__global__ __launch_bounds__(64, MPCB_WAVES_PER_SIMD) void mpcb_param_dyn(const MpcbKArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
+  if constexpr (mpcb_dyn_fuses<NOBS>) {
+    int pass = a.pass;
+#pragma clang loop unroll(disable)
+    for (;;) {
+      mpcb_solve_dyn<NOBS, false, true>(a, (int)blockIdx.x, mpcb_lds, pass);
+      if (!mpcb_second_attempt_here(a, (int)blockIdx.x, pass)) break;
+      pass = MPCB_PASS_SECOND;
+    }
+  } else {
+    mpcb_solve_dyn<NOBS, false, true>(a, (int)blockIdx.x, mpcb_lds, a.pass);
+  }
+}
+
+template <int NOBS>
+__global__ __launch_bounds__(64, 1) void mpcb_param_dyn_resto(const MpcbKArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
+  mpcb_solve_dyn<NOBS, true, true>(a, (int)blockIdx.x, mpcb_lds, MPCB_PASS_RESTO);
+}
+
 // f(x,u) of the configured model: the reference's `mpc_solver.f` (kin.py:153-159, dyn.py:156-177); host and device
 __host__ __device__ inline void model_rhs(const mpcb_config& c, const double* x, const double* u, double* xdot) {
 #pragma clang fp contract(off)   // every product and sum rounded on its own, as numpy / CasADi evaluate the reference's expressions
@@ -204,6 +252,55 @@ __global__ __launch_bounds__(128) void mpcb_advance(const mpcb_config c, int B, 
     for (int q = 0; q < NX; ++q) w[2 * N + NX * i + q] = t[q];
   }
   // obstacles move one step with constant velocity and heading (Obs_prediction.py:27-30)
+  const int nmove = move_obs == 1 ? n_obs : move_obs == 2 ? (n_obs < 1 ? n_obs : 1) : 0;
+  for (int j = 0; j < nmove; ++j) {
+    double* o = obs + ((size_t)b * n_obs + j) * 6;
+    o[0] += o[3] * cos(o[2]) * T; o[1] += o[3] * sin(o[2]) * T;
+  }
+}
+
+// mpcb_advance of the closed loop with per-instance problem data (mpcb_closed_loop_params): the plant step of instance b uses the wheelbase
+// and the vehicle / tyre constants of row b of the parameter set.  Euler only (the parameter sets exclude RK4); N, n_obs and T are
+// structural, so the shift and the obstacle advance are those of mpcb_advance.  The same expressions in the same order as mpcb_advance:
+// a mixed closed loop is bit-equal to the loops of the plain handles on their instances.
+template <int NX>
+__global__ __launch_bounds__(128) void mpcb_advance_params(const mpcb_config* __restrict__ cfgs, int B, int nz, const double* __restrict__ z,
+                                                           double* __restrict__ x0, double* __restrict__ z0, double* __restrict__ obs,
+                                                           double* __restrict__ x_hist, double* __restrict__ u_hist,
+                                                           const int32_t* __restrict__ status, int st_stride, int step, int steps,
+                                                           int move_obs, int hold, double T) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const mpcb_config& c = cfgs[b];
+  const int N = c.N, n_obs = c.n_obs;
+  double* w = z0 + (size_t)b * nz;
+  const int st_b = status ? status[(size_t)b * st_stride] : MPCB_ST_SOLVED;
+  const bool keep = hold && st_b != MPCB_ST_SOLVED && st_b != MPCB_ST_ACCEPTABLE;
+  const double* zb = keep ? w : z + (size_t)b * nz;
+  double* xb = x0 + (size_t)b * NX;
+  const double u[2] = {zb[0], zb[1]};
+  double x[MPCB_NX_MAX] = {0, 0, 0, 0, 0, 0}, f[MPCB_NX_MAX];
+#pragma unroll
+  for (int q = 0; q < NX; ++q) x[q] = xb[q];
+  model_rhs(c, x, u, f);
+#pragma unroll
+  for (int q = 0; q < NX; ++q) xb[q] = x[q] + T * f[q];
+  if (u_hist) { u_hist[((size_t)b * steps + step) * 2] = u[0]; u_hist[((size_t)b * steps + step) * 2 + 1] = u[1]; }
+  if (x_hist) {
+    double* h = x_hist + ((size_t)b * (steps + 1) + step + 1) * NX;
+#pragma unroll
+    for (int q = 0; q < NX; ++q) h[q] = xb[q];
+  }
+  for (int i = 0; i < N; ++i) { int s = (i + 1 < N) ? i + 1 : N - 1; const double a0 = zb[2 * s], a1 = zb[2 * s + 1]; w[2 * i] = a0; w[2 * i + 1] = a1; }
+  for (int i = 0; i <= N; ++i) {
+    int s = (i + 1 <= N) ? i + 1 : N;
+    double t[NX];
+#pragma unroll
+    for (int q = 0; q < NX; ++q) t[q] = zb[2 * N + NX * s + q];
+#pragma unroll
+    for (int q = 0; q < NX; ++q) w[2 * N + NX * i + q] = t[q];
+  }
   const int nmove = move_obs == 1 ? n_obs : move_obs == 2 ? (n_obs < 1 ? n_obs : 1) : 0;
   for (int j = 0; j < nmove; ++j) {
     double* o = obs + ((size_t)b * n_obs + j) * 6;
@@ -360,6 +457,14 @@ __global__ __launch_bounds__(128) void mpcb_track_window(int B, int N, double T,
 
 }  // namespace
 
+// a parameter set (mpcb_params_create): B validated configs on the handle's device, read-only from then on
+struct mpcb_params {
+  mpcb_handle* owner = nullptr;
+  int32_t B = 0;
+  mpcb_config base;                  // the handle's config the rows were validated against
+  mpcb_config* d_cfgs = nullptr;     // [B] on the owner's device
+};
+
 struct mpcb_handle {
   mpcb_config cfg;
   int device = 0;
@@ -394,6 +499,7 @@ struct mpcb_handle {
   hipEvent_t ev_sync = nullptr;                        // mpcb_stream_wait: marks "everything queued so far on this stream"
   size_t gathered_rows = 0;                            // (b): rows per shard block of the last gather, B of that solve
   int64_t gathered_B = 0;
+  std::vector<mpcb_params*> params;                    // live parameter sets of this handle (mpcb_destroy frees what the caller left)
 };
 
 namespace {
@@ -570,10 +676,15 @@ bool multi_pass(const mpcb_config& c) { return c.restoration != 0 || second_pass
 // vector (a warm start, every step of a closed loop) as 2
 int second_mode(const mpcb_config& c, const void* z0) { return c.second_start == 3 ? (z0 ? 2 : 1) : c.second_start; }
 
+// launches of the per-instance kernels; defined behind launch_solve (see there)
+int launch_param_kernel(mpcb_handle* h, hipStream_t stream, const MpcbKArgs& a, size_t lds, bool resto);
+
 // both passes of one solve on lane `lane_id` (0 = the handle's own stream)
 int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   MpcbKArgs a = a_in;
   const bool trk = a.xref != nullptr;             // per-stage reference: the mpcb_track_* kernels (kinematic model only, checked by the entry points)
+  const bool prm = a.cfgs != nullptr;             // per-instance configs: the mpcb_param_* kernels (supported combinations checked by the entry points)
+  if (prm && trk) return fail(h, MPCB_E_UNSUPPORTED, "a parameter set together with a per-stage reference");
   const size_t lds = lds_bytes(h->cfg, h->nz, trk);
   if (lds > 160 * 1024) return fail(h, MPCB_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", lds);
   if (a.B == 0) return MPCB_OK;
@@ -612,7 +723,8 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   int rc = MPCB_OK;
   auto lean_pass = [&](int pass) -> int {         // the lean main-phase kernel over the whole grid
     a.pass = pass;
-    if (trk) {
+    if (prm) rc = launch_param_kernel(h, stream, a, lds, false);
+    else if (trk) {
       if (h->cfg.obs_mode == MPCB_OBS_DCBF && h->cfg.gamma < 1.0 - 1e-12 && n > 0) {
         if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin<1, true>, a, lds);
         else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin<3, true>, a, lds);
@@ -655,7 +767,8 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
                                      : mpcbk::layout_kin(h->cfg.N, h->nz, true, mpcbk::obs_in_lds(mpcbk::obs_capacity_kin(n, is_gen(h->cfg))), wide_table(h->cfg), trk).total) * sizeof(double);
     if (lds2 > 160 * 1024) return fail(h, MPCB_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", lds2);
     const bool gen = h->cfg.obs_mode == MPCB_OBS_DCBF && h->cfg.gamma < 1.0 - 1e-12 && n > 0;
-    if (trk) {
+    if (prm) rc = launch_param_kernel(h, stream, a, lds2, true);
+    else if (trk) {
       if (gen) {
         if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin_resto<1, true>, a, lds2);
         else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin_resto<3, true>, a, lds2);
@@ -714,6 +827,30 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   return MPCB_OK;
 }
 
+// Launches of the per-instance kernels (mpcb_param_*, mpcb_advance_params).  Behind launch_solve, reached through the declaration in front
+// of it: templates are emitted in the order of their first use, and this keeps the new kernels behind the existing solve kernels in the
+// code object, whose layout then starts as it did before them.
+int launch_param_kernel(mpcb_handle* h, hipStream_t stream, const MpcbKArgs& a, size_t lds, bool resto) {
+  const int n = h->cfg.n_obs;
+  if (h->cfg.model == MPCB_MODEL_DYN) {
+    if (n <= 1) return resto ? launch_kernel(h, stream, mpcb_param_dyn_resto<1>, a, lds) : launch_kernel(h, stream, mpcb_param_dyn<1>, a, lds);
+    return resto ? launch_kernel(h, stream, mpcb_param_dyn_resto<3>, a, lds) : launch_kernel(h, stream, mpcb_param_dyn<3>, a, lds);
+  }
+  if (n == 0) return resto ? launch_kernel(h, stream, mpcb_param_kin_resto<0>, a, lds) : launch_kernel(h, stream, mpcb_param_kin<0>, a, lds);
+  if (n == 1) return resto ? launch_kernel(h, stream, mpcb_param_kin_resto<1>, a, lds) : launch_kernel(h, stream, mpcb_param_kin<1>, a, lds);
+  return resto ? launch_kernel(h, stream, mpcb_param_kin_resto<3>, a, lds) : launch_kernel(h, stream, mpcb_param_kin<3>, a, lds);
+}
+
+void launch_advance_params(int nx, hipStream_t s, const mpcb_config* d_cfgs, int B, int nz, const double* z, double* x0, double* z0, double* obs,
+                           double* x_hist, double* u_hist, const int32_t* status, int st_stride, int step, int steps, int move_obs, int hold, double T) {
+  if (nx == 6)
+    hipLaunchKernelGGL(mpcb_advance_params<6>, dim3((B + 127) / 128), dim3(128), 0, s, d_cfgs, B, nz, z, x0, z0, obs, x_hist, u_hist, status, st_stride,
+                       step, steps, move_obs, hold, T);
+  else
+    hipLaunchKernelGGL(mpcb_advance_params<4>, dim3((B + 127) / 128), dim3(128), 0, s, d_cfgs, B, nz, z, x0, z0, obs, x_hist, u_hist, status, st_stride,
+                       step, steps, move_obs, hold, T);
+}
+
 // what the tracking entry points support: the kinematic model on a single-device handle
 int check_track(mpcb_handle* h) {
   if (h->cfg.model != MPCB_MODEL_KIN) return fail(h, MPCB_E_UNSUPPORTED, "per-stage reference tracking is built for the kinematic model only");
@@ -740,7 +877,8 @@ struct Carve {
 // one launch of the solve over B instances, everything resident on the handle's device, asynchronous on its stream
 int solve_on_device(mpcb_handle* h, int32_t B, const double* d_x0, const double* d_xs, const double* d_obs, int32_t obs_kind,
                     const double* d_z0, double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, int32_t st_stride,
-                    double* d_kkt, double* d_lam_g, double* d_lam_x, int lane_id = 0, const double* d_xref = nullptr) {
+                    double* d_kkt, double* d_lam_g, double* d_lam_x, int lane_id = 0, const double* d_xref = nullptr,
+                    const mpcb_config* d_cfgs = nullptr) {
   if (B < 0 || !d_x0 || !d_xs || !d_z) return fail(h, MPCB_E_INVALID, "B < 0 or a required pointer is NULL");
   if (h->cfg.n_obs > 0 && !d_obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
   if (obs_kind != MPCB_OBSIN_STATIC && obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", obs_kind);
@@ -750,7 +888,7 @@ int solve_on_device(mpcb_handle* h, int32_t B, const double* d_x0, const double*
   a.want_mult = (d_lam_g || d_lam_x) ? 1 : 0; a.trace_instance = -1; a.trace = nullptr; a.st_stride = st_stride; a.tgrid = h->d_tgrid;
   a.x0 = d_x0; a.xs = d_xs; a.obs = d_obs; a.z0 = d_z0;
   a.z = d_z; a.obj = d_obj; a.kkt = d_kkt; a.lam_g = d_lam_g; a.lam_x = d_lam_x; a.status = d_status; a.iters = d_iters;
-  a.xref = d_xref;
+  a.xref = d_xref; a.cfgs = d_cfgs;
   return launch_solve(h, a, lane_id);
 }
 
@@ -761,11 +899,73 @@ int solve_on_device(mpcb_handle* h, int32_t B, const double* d_x0, const double*
 // into chunks: 5.5 ms per call against 4.2 ms for the single launch — so the host-pointer entries stay one launch on lane 0.
 int solve_next_lane(mpcb_handle* h, int32_t B, const double* d_x0, const double* d_xs, const double* d_obs, int32_t obs_kind,
                     const double* d_z0, double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt,
-                    double* d_lam_g, double* d_lam_x, const double* d_xref = nullptr) {
+                    double* d_lam_g, double* d_lam_x, const double* d_xref = nullptr, const mpcb_config* d_cfgs = nullptr) {
   const int K = h->lanes.empty() ? 1 : (int)h->lanes.size();
   const int lane = K == 1 ? 0 : h->next_lane;
   if (K > 1) h->next_lane = (h->next_lane + 1) % K;
-  return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, 1, d_kkt, d_lam_g, d_lam_x, lane, d_xref);
+  return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, 1, d_kkt, d_lam_g, d_lam_x, lane, d_xref, d_cfgs);
+}
+
+// ---- parameter sets: validation on the host --------------------------------------------------------------------------------------
+// The first structural field in which two configs differ, or NULL: the fields that fix the NLP's structure and the kernel that solves
+// it (every integer, T, gamma, and which entries of the boxes and rate bounds are bounds: the row pattern, ng and the layout of lam_g).
+const char* structural_diff(const mpcb_config& r, const mpcb_config& c) {
+#define MPCB_SAME(f) if (r.f != c.f) return #f
+  MPCB_SAME(struct_size); MPCB_SAME(model); MPCB_SAME(N); MPCB_SAME(n_obs); MPCB_SAME(obs_mode); MPCB_SAME(obs_terminal); MPCB_SAME(du0_cost);
+  MPCB_SAME(rate_interleaved); MPCB_SAME(max_iter); MPCB_SAME(mu_strategy); MPCB_SAME(init_rollout); MPCB_SAME(integrator); MPCB_SAME(restoration);
+  MPCB_SAME(acceptable_iter); MPCB_SAME(second_start); MPCB_SAME(T); MPCB_SAME(gamma);
+#undef MPCB_SAME
+  // "is there a bound" exactly as the kernels decide it (mk_bnd, mpcb_kernel.h: L > -1e300, U < 1e300), not std::isfinite: a +inf lower
+  // bound or a finite one of magnitude >= 1e300 is no bound to the kernel, and the row pattern of a wave must be the handle's
+#define MPCB_PATTERN_LO(f, n) for (int i = 0; i < n; ++i) if ((r.f[i] > -1e300) != (c.f[i] > -1e300)) return #f " (which entries are bounds)"
+#define MPCB_PATTERN_HI(f, n) for (int i = 0; i < n; ++i) if ((r.f[i] < 1e300) != (c.f[i] < 1e300)) return #f " (which entries are bounds)"
+  MPCB_PATTERN_LO(u_lo, MPCB_NU); MPCB_PATTERN_HI(u_hi, MPCB_NU); MPCB_PATTERN_LO(x_lo, MPCB_NX_MAX); MPCB_PATTERN_HI(x_hi, MPCB_NX_MAX);
+  MPCB_PATTERN_LO(du_lo, MPCB_NU); MPCB_PATTERN_HI(du_hi, MPCB_NU);
+#undef MPCB_PATTERN_LO
+#undef MPCB_PATTERN_HI
+  return nullptr;
+}
+
+// what the PARAMS kernels are built for, as far as the config says it
+int check_params_config(mpcb_handle* h, const mpcb_config& c) {
+  if (is_gen(c)) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets: general-gamma discrete-CBF rows have no per-instance kernel (keep-out or gamma = 1 rows only)");
+  if (c.integrator == MPCB_INT_RK4) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets: MPCB_INT_RK4 has no per-instance kernel (MPCB_INT_EULER only)");
+  if (c.n_obs > 3) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets: n_obs = %d, the per-instance kernels are built for up to 3 obstacles", c.n_obs);
+  return MPCB_OK;
+}
+
+// every row passes check_cfg and is structurally equal to `base`; the index of the first row that is not goes to *first_bad
+int check_params_rows(mpcb_handle* h, const mpcb_config& base, const mpcb_config* cfgs, int32_t B, int32_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  if (!cfgs || B < 1) return fail(h, MPCB_E_INVALID, "cfgs is NULL or B < 1");
+  { int rc = check_params_config(h, base); if (rc != MPCB_OK) return rc; }
+  for (int32_t b = 0; b < B; ++b) {
+    const char* field = structural_diff(cfgs[b], base);
+    if (field) {
+      if (first_bad) *first_bad = b;
+      return fail(h, MPCB_E_INVALID, "row %d: %s differs from the handle's config (structural fields must be equal in every row)", b, field);
+    }
+    if (check_cfg(h, &cfgs[b]) != MPCB_OK) {
+      if (first_bad) *first_bad = b;
+      const std::string why = h ? h->err : g_create_error;
+      return fail(h, MPCB_E_INVALID, "row %d: %s", b, why.c_str());
+    }
+  }
+  return MPCB_OK;
+}
+
+// may this solve of B instances on h use the set p?
+int check_params_use(mpcb_handle* h, const mpcb_params* p, int32_t B) {
+  if (!p) return fail(h, MPCB_E_INVALID, "the parameter set is NULL");
+  bool mine = false;
+  for (auto* q : h->params) mine = mine || q == p;
+  if (!mine) return fail(h, MPCB_E_INVALID, "the parameter set does not belong to this handle (or was destroyed)");
+  if (B != p->B) return fail(h, MPCB_E_INVALID, "B = %d, the parameter set holds %d rows", B, p->B);
+  if (!h->peers.empty()) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets do not run on a device group (mpcb_set_devices)");
+  if (h->d_tgrid) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets do not run with a time grid (mpcb_set_time_grid): T is structural");
+  const char* field = structural_diff(p->base, h->cfg);          // mpcb_set_bounds after mpcb_params_create may have changed the row pattern
+  if (field) return fail(h, MPCB_E_INVALID, "the handle's %s changed since the parameter set was created", field);
+  return MPCB_OK;
 }
 
 }  // namespace
@@ -859,6 +1059,7 @@ int mpcb_destroy(mpcb_handle* h) {
   collect_timing(h);
   for (auto& p : h->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
   if (h->d_buf) (void)hipFree(h->d_buf);
+  for (auto* p : h->params) { if (p->d_cfgs) (void)hipFree(p->d_cfgs); delete p; }
   for (auto* p : h->peers) mpcb_destroy(p);
   if (h->comm) { const Rccl* R = rccl(); if (R) (void)R->CommDestroy(h->comm); }
   if (h->d_gather) (void)hipFree(h->d_gather);
@@ -1003,6 +1204,7 @@ struct HostSolve {
   const double *x0, *xs, *obs, *z0; double *z, *obj, *kkt, *lam_g, *lam_x; int32_t *status, *iters;
   double *d_x0, *d_xs, *d_obs, *d_z0, *d_z, *d_obj, *d_kkt, *d_lg, *d_lx; int32_t *d_st, *d_it;
   const double* xref = nullptr; double* d_xr = nullptr;        // [B, N, 4] per-stage reference (mpcb_solve_ref), NULL = the set-point solve
+  const mpcb_config* d_cfgs = nullptr;                         // [B] per-instance configs on the device (mpcb_solve_params), NULL = the handle's config
   int issue() {
     HIP_TRY(h, hipSetDevice(h->device));
     { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
@@ -1030,7 +1232,7 @@ struct HostSolve {
     HIP_TRY(h, hipMemcpyAsync(d_xs, xs, (size_t)B * nx * 8, hipMemcpyHostToDevice, s));
     if (d_obs) HIP_TRY(h, hipMemcpyAsync(d_obs, obs, n_obs_d * 8, hipMemcpyHostToDevice, s));
     if (d_z0) HIP_TRY(h, hipMemcpyAsync(d_z0, z0, (size_t)B * nz * 8, hipMemcpyHostToDevice, s));
-    return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_st, d_it, 1, d_kkt, d_lg, d_lx, 0, d_xr);
+    return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_st, d_it, 1, d_kkt, d_lg, d_lx, 0, d_xr, d_cfgs);
   }
   int collect() {
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1197,7 +1399,7 @@ int mpcb_solve_trace(mpcb_handle* h, const double* x0, const double* xs, const d
   MpcbKArgs a;
   a.cfg = h->cfg; a.B = 1; a.nz = nz; a.ng = h->ng; a.obs_kind = obs_kind; a.want_mult = 0; a.trace_instance = 0; a.trace = d_tr; a.st_stride = 1; a.tgrid = h->d_tgrid;
   a.x0 = d_x0; a.xs = d_xs; a.obs = d_obs; a.z0 = d_z0; a.z = d_z; a.obj = nullptr; a.kkt = nullptr; a.lam_g = nullptr; a.lam_x = nullptr;
-  a.status = d_st; a.iters = d_it; a.xref = nullptr;
+  a.status = d_st; a.iters = d_it; a.xref = nullptr; a.cfgs = nullptr;
   rc = launch_solve(h, a);
   if (rc != MPCB_OK) return rc;
   HIP_TRY(h, hipMemcpyAsync(z, d_z, nz * 8, hipMemcpyDeviceToHost, s));
@@ -1212,7 +1414,7 @@ int mpcb_solve_trace(mpcb_handle* h, const double* x0, const double* xs, const d
 static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const double* x0, const double* xs, double* obs_state, int32_t obs_motion,
                             int32_t flags, double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist,
                             int32_t sample_kind, uint64_t seed, uint64_t first_index, double* x0_out, double* obs0_out,
-                            bool track = false, double aa = 0.0) {
+                            bool track = false, double aa = 0.0, const mpcb_config* d_cfgs = nullptr) {
   if (!h) return MPCB_E_INVALID;
   if (B < 0 || steps < 0 || (!sample_kind && (!x0 || !xs))) return fail(h, MPCB_E_INVALID, "B < 0, steps < 0 or a required pointer is NULL");
   if (!sample_kind && h->cfg.n_obs > 0 && !obs_state) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs_state is NULL", h->cfg.n_obs);
@@ -1273,9 +1475,11 @@ static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const doub
       HIP_TRY(h, hipGetLastError());
     }
     // the solve kernel writes status / iters of step t straight into column t of the [B, steps] histories
-    int rc = solve_on_device(h, B, d_x0, d_xs, obs_in, kind, d_z0, d_z, nullptr, d_st + t, d_it + t, steps, nullptr, nullptr, nullptr, 0, d_xr);
+    int rc = solve_on_device(h, B, d_x0, d_xs, obs_in, kind, d_z0, d_z, nullptr, d_st + t, d_it + t, steps, nullptr, nullptr, nullptr, 0, d_xr, d_cfgs);
     if (rc != MPCB_OK) return rc;
-    if (nx == 6)
+    if (d_cfgs)            // solve and plant step both from row b of the parameter set
+      launch_advance_params(nx, s, d_cfgs, B, nz, d_z, d_x0, d_z0, d_obs, d_xh, d_uh, d_st + t, steps, t, steps, move, hold, Tstep);
+    else if (nx == 6)
       hipLaunchKernelGGL(mpcb_advance<6>, dim3((B + 127) / 128), dim3(128), 0, s, h->cfg, B, nz, d_z, d_x0, d_z0, d_obs, d_xh, d_uh,
                          d_st + t, steps, t, steps, move, hold, Tstep);
     else
@@ -1306,6 +1510,87 @@ int mpcb_closed_loop_ref(mpcb_handle* h, int32_t B, int32_t steps, const double*
   if (aa == 0.0)         // every stage reference is xs: the set-point loop itself
     return closed_loop_impl(h, B, steps, x0, xs, obs_state, obs_motion, flags, x_hist, u_hist, status_hist, iters_hist, 0, 0, 0, nullptr, nullptr);
   return closed_loop_impl(h, B, steps, x0, xs, obs_state, obs_motion, flags, x_hist, u_hist, status_hist, iters_hist, 0, 0, 0, nullptr, nullptr, true, aa);
+}
+
+// ---- per-instance problem data ---------------------------------------------------------------------------------------------
+int mpcb_params_check(const mpcb_config* base, const mpcb_config* cfgs, int32_t B, int32_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  int rc = check_cfg(nullptr, base);
+  if (rc != MPCB_OK) return rc;
+  return check_params_rows(nullptr, *base, cfgs, B, first_bad);
+}
+
+int mpcb_params_create(mpcb_handle* h, const mpcb_config* cfgs, int32_t B, mpcb_params** out, int32_t* first_bad) {
+  if (first_bad) *first_bad = -1;
+  if (!h) return MPCB_E_INVALID;
+  if (!out) return fail(h, MPCB_E_INVALID, "out is NULL");
+  *out = nullptr;
+  if (!h->peers.empty()) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets do not run on a device group (mpcb_set_devices)");
+  if (h->d_tgrid) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets do not run with a time grid (mpcb_set_time_grid): T is structural");
+  { int rc = check_params_rows(h, h->cfg, cfgs, B, first_bad); if (rc != MPCB_OK) return rc; }     // host only: a kernel never sees an unvalidated row
+  HIP_TRY(h, hipSetDevice(h->device));
+  mpcb_params* p = new mpcb_params();
+  p->owner = h; p->B = B; p->base = h->cfg;
+  hipError_t e = hipMalloc(&p->d_cfgs, (size_t)B * sizeof(mpcb_config));
+  if (e == hipSuccess) e = hipMemcpy(p->d_cfgs, cfgs, (size_t)B * sizeof(mpcb_config), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (p->d_cfgs) (void)hipFree(p->d_cfgs);
+    delete p;
+    return fail(h, MPCB_E_DEVICE, "uploading %d configs: %s", B, hipGetErrorString(e));
+  }
+  h->params.push_back(p);
+  *out = p;
+  return MPCB_OK;
+}
+
+int mpcb_params_destroy(mpcb_handle* h, mpcb_params* p) {
+  if (!h) return MPCB_E_INVALID;
+  if (!p) return MPCB_OK;
+  size_t at = h->params.size();
+  for (size_t i = 0; i < h->params.size(); ++i) if (h->params[i] == p) at = i;
+  if (at == h->params.size()) return fail(h, MPCB_E_INVALID, "the parameter set does not belong to this handle (or was destroyed)");
+  { int rc = mpcb_sync(h); if (rc != MPCB_OK) return rc; }       // lanes joined, nothing in flight still reads the rows
+  h->params.erase(h->params.begin() + at);
+  HIP_TRY(h, hipFree(p->d_cfgs));
+  delete p;
+  return MPCB_OK;
+}
+
+int mpcb_solve_params(mpcb_handle* h, int32_t B, const mpcb_params* p, const double* x0, const double* xs, const double* obs, int32_t obs_kind,
+                      const double* z0, double* z, double* obj, int32_t* status, int32_t* iters, double* kkt, double* lam_g, double* lam_x) {
+  if (!h) return MPCB_E_INVALID;
+  { int rc = check_params_use(h, p, B); if (rc != MPCB_OK) return rc; }
+  if (!x0 || !xs || !z) return fail(h, MPCB_E_INVALID, "a required pointer is NULL");
+  if (h->cfg.n_obs > 0 && !obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
+  if (obs_kind != MPCB_OBSIN_STATIC && obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", obs_kind);
+  HostSolve q{};
+  q.h = h; q.B = B; q.obs_kind = obs_kind; q.x0 = x0; q.xs = xs; q.obs = obs; q.z0 = z0; q.d_cfgs = p->d_cfgs;
+  q.z = z; q.obj = obj; q.kkt = kkt; q.lam_g = lam_g; q.lam_x = lam_x; q.status = status; q.iters = iters;
+  int rc = q.issue();
+  if (rc != MPCB_OK) return rc;
+  rc = q.collect();
+  if (rc != MPCB_OK) return rc;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MPCB_OK;
+}
+
+int mpcb_solve_device_params(mpcb_handle* h, int32_t B, const mpcb_params* p, const double* d_x0, const double* d_xs, const double* d_obs,
+                             int32_t obs_kind, const double* d_z0, double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt,
+                             double* d_lam_g, double* d_lam_x, int32_t sync) {
+  if (!h) return MPCB_E_INVALID;
+  { int rc = check_params_use(h, p, B); if (rc != MPCB_OK) return rc; }
+  int rc = solve_next_lane(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, d_kkt, d_lam_g, d_lam_x, nullptr, p->d_cfgs);
+  if (rc != MPCB_OK) return rc;
+  if (sync) return mpcb_sync(h);
+  return MPCB_OK;
+}
+
+int mpcb_closed_loop_params(mpcb_handle* h, int32_t B, int32_t steps, const mpcb_params* p, const double* x0, const double* xs, double* obs_state,
+                            int32_t obs_motion, int32_t flags, double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist) {
+  if (!h) return MPCB_E_INVALID;
+  { int rc = check_params_use(h, p, B); if (rc != MPCB_OK) return rc; }
+  return closed_loop_impl(h, B, steps, x0, xs, obs_state, obs_motion, flags, x_hist, u_hist, status_hist, iters_hist, 0, 0, 0, nullptr, nullptr,
+                          false, 0.0, p->d_cfgs);
 }
 
 int mpcb_closed_loop_sampled(mpcb_handle* h, int32_t kind, int32_t B, uint64_t seed, uint64_t first_index, int32_t steps, int32_t obs_motion,

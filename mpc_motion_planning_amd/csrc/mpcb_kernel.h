@@ -45,6 +45,8 @@ struct MpcbKArgs {
   int32_t *status, *iters;
   double* trace;   // optional: [max_iter + 1][8] log of instance trace_instance (debug / parity tests)
   const double* xref;  // [B][N][4] per-stage reference of the tracking kernels (mpcb_solve_ref): row i replaces xs in stage i's cost; NULL elsewhere
+  const mpcb_config* cfgs;  // [B] per-instance configs of the PARAMS kernels (mpcb_solve_params): validated rows, structurally equal to cfg; NULL elsewhere.
+                            // The last member: the offsets of every field above are those of the kernels that never read it.
 };
 
 // MPCB_STAMPS (diagnostic build only, never shipped): overwrite trace columns 4..7 with cycle counts of the phases of
@@ -74,6 +76,14 @@ struct MpcbKArgs {
 #define MPCB_PASS_RESTO 2
 
 namespace mpcbk {
+
+// The config an instance is solved under, re-addressed at the point of use (see wv::late_args): the handle's config inside the kernel
+// arguments, or, in the PARAMS instantiations, row b of the parameter set's table (wv::late_row).  `if constexpr`, never a run-time
+// select between the two addresses: that would turn every config read into a FLAT load (see T_ in mpcb_solve_kin).
+template <bool PARAMS> MPCB_DEV const mpcb_config& cfg_late(const MpcbKArgs& a, const int b) {
+  if constexpr (PARAMS) return *wv::late_row(wv::late_args(a)->cfgs, b);
+  else return wv::late_args(a)->cfg;
+}
 
 constexpr int NU = 2;
 constexpr int FILTER_MAX = 64;
@@ -294,16 +304,22 @@ constexpr double DW_FIRST = 1e-4, DW_MIN = 1e-20, DW_MAX = 1e40, KW_MINUS = 1.0 
 // TRACK = per-stage reference tracking (mpcb_solve_ref): stage i's cost is (X_i - r_i)' Q (X_i - r_i) with r_i = a.xref[b][i] instead of
 //   xs (kin.py:194-199 with ref_X_i = aa * ref_state[i+1] + (1 - aa) * xs).  The reference lives in LDS (layout row block `trk`), read per
 //   lane where the other kernels read the uniform set-point; the Hessian is unchanged.
-template <int NOBS, bool GEN = false, bool RESTO = false, bool RK4 = false, bool TRACK = false>
+// PARAMS = per-instance problem data (mpcb_solve_params): every config read goes to row b of a.cfgs instead of a.cfg.  The rows are
+//   validated on the host to be structurally equal to a.cfg (N, n_obs, modes, T, gamma, row pattern), so one wave = one instance stays
+//   wave-uniform and the fields still arrive by scalar loads.  Euler, keep-out / gamma = 1 rows, NOBS <= 3, never with TRACK.
+template <int NOBS, bool GEN = false, bool RESTO = false, bool RK4 = false, bool TRACK = false, bool PARAMS = false>
 MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, const int pass) {   // pass: MPCB_PASS_* (see MpcbKArgs::pass; a parameter of its own because one launch can run two passes of an instance)
   // every kernel argument is read through a pointer the optimiser cannot see through (wv::late_args): the compiler then loads a field
   // where the code needs it instead of preloading the whole 800-byte argument block into scalar registers at entry, most of which it
   // has to spill into VGPR lanes again (kin<3>: 806 -> 582 v_readlane of SGPR reloads)
   const MpcbKArgs& a = *wv::late_args(a_in);
   static_assert(!(GEN && RK4), "general-gamma CBF rows are written for the Euler step");
+  static_assert(!PARAMS || (!GEN && !RK4 && !TRACK && NOBS <= 3), "per-instance configs: Euler, keep-out / gamma = 1 rows, up to 3 obstacles, no tracking");
   using namespace mpcbk;
   constexpr int NX = 4, NA = 6, NW = 8, NOB = NOBS > 0 ? NOBS : 1, NEL = RESTO ? NOB : 1;
-  const mpcb_config& c = a.cfg;
+  const mpcb_config* cp_ = &a.cfg;
+  if constexpr (PARAMS) cp_ = wv::late_row(a.cfgs, b);           // row b of the parameter set: uniform, constant address space
+  const mpcb_config& c = *cp_;
   // (the lane index opaque: nothing derived from it is hoisted out of the attempt loop of the fusing kernels and kept alive across attempts)
   const int N = c.N, lane = wv::opaque(wv::lane()), k = lane;
   const int nz = a.nz, nobs = c.n_obs;
@@ -577,7 +593,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
     // cfg.start_steer (include/mpcbatch.h; oracle: Solver::init): a cold start whose straight roll-out passes an obstacle row closer than
     // h - obs_hmin < 1 is rolled out with a slight constant turn instead — away from the centre of that obstacle (the first minimum of
     // h over the nodes, then over the obstacles of a node), or to its other side when the y box has no room for the row's ellipse there
-    if (NOBS > 0 && !a.z0 && nobs > 0 && wv::late_args(a)->cfg.start_steer > 0.0) {       // wave-uniform
+    if (NOBS > 0 && !a.z0 && nobs > 0 && cfg_late<PARAMS>(a, b).start_steer > 0.0) {       // wave-uniform
       double hm = 1e300, oyk = 0.0, iyk = 1.0;
 #pragma unroll
       for (int j = 0; j < NOBS; ++j) if (j < nobs) {
@@ -592,7 +608,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
         double sgn = py >= qy ? 1.0 : -1.0;
         const bool up = qy + sy <= c.x_hi[1], dn = qy - sy >= c.x_lo[1];
         if (sgn > 0 && !up && dn) sgn = -1.0; else if (sgn < 0 && !dn && up) sgn = 1.0;
-        U[0] = hasu ? sgn * wv::late_args(a)->cfg.start_steer : 0.0;
+        U[0] = hasu ? sgn * cfg_late<PARAMS>(a, b).start_steer : 0.0;
         roll_out();
       }
     }
@@ -1031,7 +1047,7 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
           // complementarity of the scaled problem divided by the objective scaling; there is no constraint scaling); then the
           // acceptable-point counter with the reference's two options (kin.py:252-253)
           const double compl0 = n_vr > 0 ? sv_hi : 0.0;
-          const auto* lc = &wv::late_args(a)->cfg;       // the nine tolerances are loaded here, once per iteration, and are dead again after the test
+          const auto* lc = &cfg_late<PARAMS>(a, b);      // the nine tolerances are loaded here, once per iteration, and are dead again after the test
           if (err0 <= lc->tol && e_dual <= lc->dual_inf_tol * os && e_prim <= lc->constr_viol_tol && compl0 <= lc->compl_inf_tol * os) { status = MPCB_ST_SOLVED; break; }
           const double fcur = os * fval;
           const bool acc = lc->acceptable_iter > 0 && err0 <= lc->acceptable_tol && e_dual <= lc->acceptable_dual_inf_tol * os &&

@@ -132,8 +132,8 @@ MPCB_DEV void dyn_hess(const mpcb_config& c, const double T, const double* X, co
 
 }  // namespace mpcbk
 
-// RESTO: the instantiation of the restoration pass (see mpcb_solve_kin)
-template <int NOBS, bool RESTO = false>
+// RESTO: the instantiation of the restoration pass; PARAMS: per-instance problem data, every config read from row b of a.cfgs (see mpcb_solve_kin)
+template <int NOBS, bool RESTO = false, bool PARAMS = false>
 MPCB_DEVFN void mpcb_solve_dyn(const MpcbKArgs& a_in, const int b, double* lds, const int pass) {   // pass: MPCB_PASS_* (see MpcbKArgs::pass; a parameter of its own because one launch can run two passes of an instance)
   // every kernel argument is read through a pointer the optimiser cannot see through (wv::late_args): the compiler then loads a field
   // where the code needs it instead of preloading the whole 800-byte argument block into scalar registers at entry, most of which it
@@ -141,10 +141,13 @@ MPCB_DEVFN void mpcb_solve_dyn(const MpcbKArgs& a_in, const int b, double* lds, 
   const MpcbKArgs& a = *wv::late_args(a_in);
   using namespace mpcbk;
   constexpr int NX = 6, NA = 8, NW = 10, NOB = NOBS > 0 ? NOBS : 1, NEL = RESTO ? NOB : 1;
-  const mpcb_config& c = a.cfg;
+  static_assert(!PARAMS || NOBS <= 3, "per-instance configs: up to 3 obstacles");
+  const mpcb_config* cp_ = &a.cfg;
+  if constexpr (PARAMS) cp_ = wv::late_row(a.cfgs, b);           // row b of the parameter set: uniform, constant address space
+  const mpcb_config& c = *cp_;
   // the eight vehicle / tyre constants of the model are loaded from the kernel arguments at every model evaluation instead of living in
   // 16+ scalar registers for the whole solve (wv::late_args): the dyn kernels spill SGPRs into VGPR lanes by the hundred
-  auto MC = [&]() -> const mpcb_config& { return wv::late_args(a)->cfg; };
+  auto MC = [&]() -> const mpcb_config& { return cfg_late<PARAMS>(a, b); };
   const int N = c.N, lane = wv::opaque(wv::lane()), k = lane;     // (opaque: see mpcb_kernel.h)
   const int nz = a.nz, nobs = c.n_obs;
   if (RESTO && a.status[(size_t)b * a.st_stride] != MPCB_ST_NEEDS_RESTO) return;     // wave-uniform: this instance is done
@@ -742,7 +745,7 @@ MPCB_DEVFN void mpcb_solve_dyn(const MpcbKArgs& a_in, const int b, double* lds, 
           // complementarity of the scaled problem divided by the objective scaling; there is no constraint scaling); then the
           // acceptable-point counter with the reference's two options (kin.py:252-253)
           const double compl0 = n_vr > 0 ? sv_hi : 0.0;
-          const auto* lc = &wv::late_args(a)->cfg;       // the nine tolerances are loaded here, once per iteration, and are dead again after the test
+          const auto* lc = &cfg_late<PARAMS>(a, b);      // the nine tolerances are loaded here, once per iteration, and are dead again after the test
           if (err0 <= lc->tol && e_dual <= lc->dual_inf_tol * os && e_prim <= lc->constr_viol_tol && compl0 <= lc->compl_inf_tol * os) { status = MPCB_ST_SOLVED; break; }
           const double fcur = os * fval;
           const bool acc = lc->acceptable_iter > 0 && err0 <= lc->acceptable_tol && e_dual <= lc->acceptable_dual_inf_tol * os &&

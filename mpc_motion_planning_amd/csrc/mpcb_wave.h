@@ -106,6 +106,16 @@ template <class T> MPCB_DEV const T* late_args(const T&) {
   const unsigned long long p = ((unsigned long long)hi << 32) | lo;
   return (const T*)(const __attribute__((address_space(4))) T*)p;      // constant address space: scalar loads
 }
+// Row `row` (wave-uniform) of a read-only table in device memory, addressed the way late_args addresses the argument block: the
+// pointer is made uniform, hidden from the optimiser and put into the constant address space, so that a field read through it is a
+// scalar load at the point of use.  The table must not be written while the kernel runs (the scalar cache is not coherent).
+template <class T> MPCB_DEV const T* late_row(const T* table, int row) {
+  const unsigned long long p0 = (unsigned long long)(table + row);
+  unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)p0), hi = __builtin_amdgcn_readfirstlane((unsigned)(p0 >> 32));
+  asm volatile("" : "+s"(lo), "+s"(hi));
+  const unsigned long long p = ((unsigned long long)hi << 32) | lo;
+  return (const T*)(const __attribute__((address_space(4))) T*)p;
+}
 // a wave-uniform double moved to scalar registers
 MPCB_DEV double uni(double v) {
   int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
@@ -169,6 +179,7 @@ template <int NS, int NM> inline void reduce(double* s, double* m) {
 }
 inline int opaque(int v) { return v; }
 template <class T> inline const T* late_args(const T& a) { return &a; }
+template <class T> inline const T* late_row(const T* table, int row) { return table + row; }
 inline double uni(double v) { return v; }
 inline double rcp(double x) { return 1.0 / x; }
 }  // namespace wv

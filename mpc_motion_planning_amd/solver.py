@@ -53,6 +53,67 @@ def model_rhs(cfg, x, u):
     return out
 
 
+def vary(cfg, B, **fields):
+    """A ctypes array of B configs copied from `cfg`, with each named field set per instance from an array of shape [B] (scalar
+    fields) or [B, k] (array fields of length k):  vary(cfg, B, Q=q[B,4], veh_l=l[B]).  An array field may be given fewer columns
+    than it has (Q is [6], the kinematic model uses 4); the rest keep cfg's values.  The result is what BatchSolver.params takes."""
+    B = int(B)
+    if B < 1:
+        raise ValueError("B must be >= 1")
+    types = dict(MpcbConfig._fields_)
+    cols = {}
+    for name, val in fields.items():
+        if name not in types:
+            raise ValueError("mpcb_config has no field %r" % name)
+        ftype = types[name]
+        v = np.asarray(val)
+        if issubclass(ftype, C.Array):
+            if v.ndim != 2 or v.shape[0] != B or not 1 <= v.shape[1] <= ftype._length_:
+                raise ValueError("%s must be [B, k] = [%d, 1..%d], got %s" % (name, B, ftype._length_, v.shape))
+            cols[name] = v.astype(np.float64)
+        else:
+            if v.shape != (B,):
+                raise ValueError("%s must be [B] = [%d], got %s" % (name, B, v.shape))
+            if ftype is C.c_double:
+                cols[name] = v.astype(np.float64)
+            else:
+                if not np.all(np.asarray(v, dtype=np.float64) == np.round(np.asarray(v, dtype=np.float64))):
+                    raise ValueError("%s is an integer field, got non-integral values" % name)
+                cols[name] = np.asarray(v, dtype=np.float64).astype(np.int64)
+    out = (MpcbConfig * B)()
+    for b in range(B):
+        C.memmove(C.byref(out[b]), C.byref(cfg), C.sizeof(MpcbConfig))
+        for name, v in cols.items():
+            if v.ndim == 2:
+                arr = getattr(out[b], name)
+                for i in range(v.shape[1]):
+                    arr[i] = v[b, i]
+            else:
+                setattr(out[b], name, v[b].item())
+    return out
+
+
+class ParamSet:
+    """A validated, device-resident, read-only set of per-instance configs (mpcb_params_create); made by BatchSolver.params.
+    Pass it as `params=` to solve_batch / solve_device / closed_loop; close() it (or use it as a context manager) before the solver.
+    Closing the solver first is safe as well: mpcb_destroy frees the sets it still holds, and close() then has nothing left to do."""
+
+    def __init__(self, solver, ptr, B):
+        self.solver, self.ptr, self.B = solver, ptr, int(B)
+
+    def close(self):
+        if self.ptr is not None and self.solver._h:
+            check(lib().mpcb_params_destroy(self.solver._h, self.ptr), self.solver._h)
+        self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class DeviceArray:
     """A caller-owned device buffer (row-major, float64 or int32)."""
 
@@ -141,9 +202,31 @@ class BatchSolver:
             return obs.reshape(B, n, self.N + 1, 6), _abi.OBSIN_PREDICTED
         raise ValueError("obs has %d values; expected [B,%d,6] or [B,%d,%d,6]" % (obs.size, n, n, self.N + 1))
 
-    def solve_batch(self, x0, xs, obs=None, z0=None, multipliers=False, x_ref=None):
+    def params(self, cfgs):
+        """A ParamSet from B configs (the array vary() returns, or a sequence of MpcbConfig): row b is the config instance b is solved
+        under.  Every row must pass the checks of BatchSolver(cfg) and equal this solver's config in every structural field
+        (include/mpcbatch.h, mpcb_params_create); a row that does not raises ValueError with the library's message and the row's index."""
+        if not (isinstance(cfgs, C.Array) and cfgs._type_ is MpcbConfig):
+            rows = list(cfgs)
+            arr = (MpcbConfig * len(rows))()
+            for b, r in enumerate(rows):
+                C.memmove(C.byref(arr[b]), C.byref(r), C.sizeof(MpcbConfig))
+            cfgs = arr
+        B = len(cfgs)
+        p = C.c_void_p(); bad = C.c_int32(-1)
+        rc = lib().mpcb_params_create(self._h, cfgs, B, C.byref(p), C.byref(bad))
+        if rc == _abi.E_INVALID:
+            msg = lib().mpcb_last_error(self._h)
+            raise ValueError("parameter set rejected, first bad row %d: %s" % (bad.value, msg.decode("utf-8", "replace") if msg else ""))
+        check(rc, self._h)
+        return ParamSet(self, p, B)
+
+    def solve_batch(self, x0, xs, obs=None, z0=None, multipliers=False, x_ref=None, params=None):
         """x0, xs [B,nx]; obs [B,n_obs,6] | [B,n_obs,N+1,6]; z0 [B,nz] | None  ->  dict(z, obj, status, iters, kkt[, lam_g, lam_x])
-        x_ref [B,N,nx] | None: per-stage reference, row i replaces xs in stage i's cost (mpcb_solve_ref; kinematic model only)."""
+        x_ref [B,N,nx] | None: per-stage reference, row i replaces xs in stage i's cost (mpcb_solve_ref; kinematic model only).
+        params: a ParamSet of B rows, instance b is solved under row b (mpcb_solve_params); not together with x_ref."""
+        if params is not None and x_ref is not None:
+            raise ValueError("params and x_ref cannot be combined: the parameter sets have no tracking kernels")
         x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
         xs = np.ascontiguousarray(np.atleast_2d(np.asarray(xs, dtype=np.float64)))
         B = x0.shape[0]
@@ -160,7 +243,10 @@ class BatchSolver:
         kkt = np.empty((B, 4))
         lam_g = np.empty((B, self.ng)) if multipliers else None
         lam_x = np.empty((B, self.nz)) if multipliers else None
-        if x_ref is None:
+        if params is not None:
+            check(lib().mpcb_solve_params(self._h, B, params.ptr, dptr(x0), dptr(xs), dptr(obs), kind, dptr(z0), dptr(z), dptr(obj), iptr(st),
+                                          iptr(it), dptr(kkt), dptr(lam_g), dptr(lam_x)), self._h)
+        elif x_ref is None:
             check(lib().mpcb_solve(self._h, B, dptr(x0), dptr(xs), dptr(obs), kind, dptr(z0), dptr(z), dptr(obj), iptr(st),
                                    iptr(it), dptr(kkt), dptr(lam_g), dptr(lam_x)), self._h)
         else:
@@ -183,18 +269,21 @@ class BatchSolver:
         return dict(z=z[0], status=int(st[0]), iters=int(it[0]), trace=tr[: int(it[0]) + 1])
 
     def closed_loop(self, x0, xs, obs_state=None, steps=80, obs_motion=_abi.OBSMOVE_STATIC, hold_on_failure=False,
-                    advance_first_only=False, aa=0.0):
+                    advance_first_only=False, aa=0.0, params=None):
         """Receding-horizon loop on the device (main_cbf_kin_c_sim.py:87-123).  obs_motion: OBSMOVE_STATIC (obstacles fixed,
         main_cbf_kin_c_sim.py), OBSMOVE_PREDICTED (constant-velocity obstacles predicted per solve and advanced per step,
         main_cbf_kin_c_sim_pre.py), OBSMOVE_CURRENT (advanced, no prediction).
         hold_on_failure: a step whose solve fails applies the previous plan (hold-and-shift) instead of the failed iterate.
         advance_first_only: only obstacle 0 moves between steps (main_cbf_kin_c_sim_pre.py:106).
         aa: blend weight of the path window in the stage cost (kin.py:194-199, mpcb_closed_loop_ref); 0 = the set-point loop.
+        params: a ParamSet of B rows: solve and plant step of instance b under row b (mpcb_closed_loop_params); not with aa != 0.
         Returns dict(x_hist, u_hist, status, iters, obs_state)."""
         x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
         xs = np.ascontiguousarray(np.atleast_2d(np.asarray(xs, dtype=np.float64)))
         B = x0.shape[0]
         aa = float(aa)
+        if params is not None and aa != 0.0:
+            raise ValueError("params and aa != 0 cannot be combined: the parameter sets have no tracking kernels")
         if aa != 0.0:
             if x0.shape != (B, self.nx) or xs.shape != (B, self.nx):
                 raise ValueError("x0 and xs must be [B,%d]" % self.nx)
@@ -204,7 +293,10 @@ class BatchSolver:
         xh = np.empty((B, steps + 1, self.nx)); uh = np.empty((B, steps, 2))
         st = np.empty((B, steps), np.int32); it = np.empty((B, steps), np.int32)
         flags = (_abi.CL_HOLD_ON_FAILURE if hold_on_failure else 0) | (_abi.CL_ADVANCE_FIRST_ONLY if advance_first_only else 0)
-        if aa == 0.0:
+        if params is not None:
+            check(lib().mpcb_closed_loop_params(self._h, B, steps, params.ptr, dptr(x0), dptr(xs), dptr(ob), int(obs_motion), flags, dptr(xh),
+                                                dptr(uh), iptr(st), iptr(it)), self._h)
+        elif aa == 0.0:
             check(lib().mpcb_closed_loop(self._h, B, steps, dptr(x0), dptr(xs), dptr(ob), int(obs_motion), flags, dptr(xh), dptr(uh),
                                          iptr(st), iptr(it)), self._h)
         else:
@@ -258,16 +350,21 @@ class BatchSolver:
         return DeviceArray(self, shape, dtype)
 
     def solve_device(self, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj=None, d_status=None, d_iters=None, d_kkt=None,
-                     d_lam_g=None, d_lam_x=None, sync=False, d_x_ref=None):
+                     d_lam_g=None, d_lam_x=None, sync=False, d_x_ref=None, params=None):
         """Raw device pointers (ints / c_void_p / DeviceArray).  Asynchronous on the handle's stream unless sync.
-        d_x_ref [B,N,nx]: per-stage reference (mpcb_solve_device_ref)."""
+        d_x_ref [B,N,nx]: per-stage reference (mpcb_solve_device_ref).  params: a ParamSet of B rows (mpcb_solve_device_params)."""
+        if params is not None and d_x_ref is not None:
+            raise ValueError("params and d_x_ref cannot be combined: the parameter sets have no tracking kernels")
         def p(v):
             if v is None:
                 return None
             if isinstance(v, DeviceArray):
                 return v.ptr
             return C.c_void_p(int(v)) if not isinstance(v, C.c_void_p) else v
-        if d_x_ref is None:
+        if params is not None:
+            check(lib().mpcb_solve_device_params(self._h, B, params.ptr, p(d_x0), p(d_xs), p(d_obs), obs_kind, p(d_z0), p(d_z), p(d_obj),
+                                                 p(d_status), p(d_iters), p(d_kkt), p(d_lam_g), p(d_lam_x), 1 if sync else 0), self._h)
+        elif d_x_ref is None:
             check(lib().mpcb_solve_device(self._h, B, p(d_x0), p(d_xs), p(d_obs), obs_kind, p(d_z0), p(d_z), p(d_obj), p(d_status),
                                           p(d_iters), p(d_kkt), p(d_lam_g), p(d_lam_x), 1 if sync else 0), self._h)
         else:
