@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "mpcb_kernel_dyn.h"
+#include "mpcb_dispatch.h"
 
 #ifndef MPCB_WAVES_PER_SIMD
 #define MPCB_WAVES_PER_SIMD 1
@@ -28,19 +29,10 @@ namespace {
 constexpr double INF = std::numeric_limits<double>::infinity();
 thread_local std::string g_create_error;
 
-// Second attempt inside the first launch (second start of kind 1, the cold-start batches): the wave whose first attempt failed starts
-// over from z = 0 at once instead of in a second launch that can only begin when the slowest first attempt of the batch has finished.
-// Only the instantiations with registers to spare do this (kin<0>, kin<1>: +17 AGPRs; measured C2 +2.5 % with six lanes, +11 % with one
-// launch at a time): the loop around the inlined solve keeps loop-invariant per-lane values alive across both attempts, which costs
-// kin<3> 200 -> 256 AGPRs + 124 B of scratch (C3 -9 %) and dyn<3> 236 -> 256 + 452 B (C4 -7 %).  Those launch the second attempt as a
-// pass of its own (launch_solve).  -DMPCB_NO_FUSED_SECOND: no instantiation fuses (A/B builds).
-#ifdef MPCB_NO_FUSED_SECOND
-template <int NOBS, bool GEN, bool RK4> constexpr bool mpcb_kin_fuses = false;
-template <int NOBS> constexpr bool mpcb_dyn_fuses = false;
-#else
-template <int NOBS, bool GEN, bool RK4> constexpr bool mpcb_kin_fuses = NOBS <= 3 && !GEN && !RK4;
-template <int NOBS> constexpr bool mpcb_dyn_fuses = NOBS <= 3;
-#endif
+// Which instantiation fuses its second attempt into the first launch is decided in mpcb_dispatch.h (mpcbd::fuses): the kernels'
+// `if constexpr` and the pass plan of launch_solve read the same function.
+template <int NOBS, bool GEN, bool RK4> constexpr bool mpcb_kin_fuses = mpcbd::fuses(NOBS, GEN, RK4);
+template <int NOBS> constexpr bool mpcb_dyn_fuses = mpcbd::fuses(NOBS, false, false);
 __host__ __device__ inline bool mpcb_second_kind1(const mpcb_config& c, const void* z0) {   // cfg.second_start = 3: by the kind of start
   return c.init_rollout && (c.second_start == 1 || (c.second_start == 3 && !z0));
 }
@@ -596,13 +588,10 @@ int check_cfg(mpcb_handle* h, const mpcb_config* c) {
   return MPCB_OK;
 }
 
-bool is_gen(const mpcb_config& c) { return c.model == MPCB_MODEL_KIN && c.obs_mode == MPCB_OBS_DCBF && c.gamma < 1.0 - 1e-12 && c.n_obs > 0; }
-bool is_rk4(const mpcb_config& c) { return c.model == MPCB_MODEL_KIN && c.integrator == MPCB_INT_RK4; }
-bool wide_table(const mpcb_config& c) { return is_gen(c) || is_rk4(c); }       // four more rows in the entry table of the kinematic kernels
-
-size_t lds_bytes(const mpcb_config& c, int nz, bool track = false) {
-  return (size_t)(c.model == MPCB_MODEL_DYN ? mpcbk::layout_dyn(c.N, false, mpcbk::obs_in_lds(mpcbk::obs_capacity_dyn(c.n_obs))).total
-                                             : mpcbk::layout_kin(c.N, nz, false, mpcbk::obs_in_lds(mpcbk::obs_capacity_kin(c.n_obs, is_gen(c))), wide_table(c), track).total) * sizeof(double);
+// the variant (mpcb_dispatch.h) that serves cfg with or without a per-stage reference / a parameter set, or the error of having none
+int variant_or_fail(mpcb_handle* h, const mpcb_config& c, bool track, bool params, mpcbd::Variant* v) {
+  const mpcbd::Refusal r = mpcbd::variant_of(c, track, params, v);
+  return r.code == MPCB_OK ? MPCB_OK : fail(h, r.code, r.fmt, c.n_obs);
 }
 
 // oldest recorded pair -> total_ms / last_ms / launches
@@ -670,23 +659,29 @@ int ensure_lanes(mpcb_handle* h, int k) {
   return MPCB_OK;
 }
 
-bool second_pass(const mpcb_config& c) { return c.second_start != 0 && c.init_rollout != 0; }      // a second start exists only after a roll-out start
-bool multi_pass(const mpcb_config& c) { return c.restoration != 0 || second_pass(c); }
-// cfg.second_start = 3: the order of the passes follows the kind of start — a cold start (z0 = NULL) behaves as 1, a solve with a start
-// vector (a warm start, every step of a closed loop) as 2
-int second_mode(const mpcb_config& c, const void* z0) { return c.second_start == 3 ? (z0 ? 2 : 1) : c.second_start; }
+// The __global__ of an instantiation tag (mpcbd::Inst): the only place that names the solve kernels.
+template <class T> constexpr auto kernel_of(T) {
+  constexpr int n = T::nobs;
+  constexpr bool g = T::gen, r = T::rk4;
+  if constexpr (T::model == MPCB_MODEL_DYN) {
+    if constexpr (T::params) { if constexpr (T::resto) return mpcb_param_dyn_resto<n>; else return mpcb_param_dyn<n>; }
+    else { if constexpr (T::resto) return mpcb_kernel_dyn_resto<n>; else return mpcb_kernel_dyn<n>; }
+  } else if constexpr (T::params) { if constexpr (T::resto) return mpcb_param_kin_resto<n>; else return mpcb_param_kin<n>; }
+  else if constexpr (T::track) { if constexpr (T::resto) return mpcb_track_kin_resto<n, g, r>; else return mpcb_track_kin<n, g, r>; }
+  else { if constexpr (T::resto) return mpcb_kernel_kin_resto<n, g, r>; else return mpcb_kernel_kin<n, g, r>; }
+}
 
-// launches of the per-instance kernels; defined behind launch_solve (see there)
-int launch_param_kernel(mpcb_handle* h, hipStream_t stream, const MpcbKArgs& a, size_t lds, bool resto);
-
-// both passes of one solve on lane `lane_id` (0 = the handle's own stream)
+// every pass of one solve on lane `lane_id` (0 = the handle's own stream): a.xref selects the tracking kernels, a.cfgs the per-instance ones
 int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   MpcbKArgs a = a_in;
-  const bool trk = a.xref != nullptr;             // per-stage reference: the mpcb_track_* kernels (kinematic model only, checked by the entry points)
-  const bool prm = a.cfgs != nullptr;             // per-instance configs: the mpcb_param_* kernels (supported combinations checked by the entry points)
-  if (prm && trk) return fail(h, MPCB_E_UNSUPPORTED, "a parameter set together with a per-stage reference");
-  const size_t lds = lds_bytes(h->cfg, h->nz, trk);
-  if (lds > 160 * 1024) return fail(h, MPCB_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", lds);
+  mpcbd::Variant v;
+  { int rc = variant_or_fail(h, h->cfg, a.xref != nullptr, a.cfgs != nullptr, &v); if (rc != MPCB_OK) return rc; }
+  const mpcbd::Plan plan = mpcbd::pass_plan(h->cfg, a.z0 != nullptr, mpcbd::fuses(v));
+  const size_t lds[2] = {mpcbd::lds_bytes(v, h->cfg.N, false), mpcbd::lds_bytes(v, h->cfg.N, true)};     // [pass is the restoration pass]
+  for (int i = 0; i < plan.n; ++i) {
+    const size_t need = lds[plan.pass[i] == MPCB_PASS_RESTO];
+    if (need > mpcbd::LDS_MAX_BYTES) return fail(h, MPCB_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", need);
+  }
   if (a.B == 0) return MPCB_OK;
   if (h->lanes.empty()) { int rc = ensure_lanes(h, 1); if (rc != MPCB_OK) return rc; }
   mpcb_handle::Lane& L = h->lanes[lane_id];
@@ -695,8 +690,8 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
     HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
     HIP_TRY(h, hipStreamWaitEvent(stream, h->ev_fork, 0));
   }
-  a.pass = MPCB_PASS_FIRST; a.work = nullptr;
-  if (multi_pass(h->cfg)) {
+  a.work = nullptr;
+  if (mpcbd::multi_pass(h->cfg)) {
     if (a.B > L.work_cap) {       // grows with the largest batch seen (first call of a given size only)
       HIP_TRY(h, hipStreamSynchronize(stream));
       if (L.d_work) HIP_TRY(h, hipFree(L.d_work));
@@ -719,126 +714,19 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   if (h->ev_pending == mpcb_handle::EV_RING) { int rc = harvest_one(h); if (rc != MPCB_OK) return rc; }
   auto& evp = h->ev[h->ev_head];
   HIP_TRY(h, hipEventRecord(evp.first, stream));
-  const int n = h->cfg.n_obs;
-  int rc = MPCB_OK;
-  auto lean_pass = [&](int pass) -> int {         // the lean main-phase kernel over the whole grid
-    a.pass = pass;
-    if (prm) rc = launch_param_kernel(h, stream, a, lds, false);
-    else if (trk) {
-      if (h->cfg.obs_mode == MPCB_OBS_DCBF && h->cfg.gamma < 1.0 - 1e-12 && n > 0) {
-        if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin<1, true>, a, lds);
-        else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin<3, true>, a, lds);
-        else rc = launch_kernel(h, stream, mpcb_track_kin<8, true>, a, lds);
-      } else if (is_rk4(h->cfg)) {
-        if (n == 0) rc = launch_kernel(h, stream, mpcb_track_kin<0, false, true>, a, lds);
-        else if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin<1, false, true>, a, lds);
-        else rc = launch_kernel(h, stream, mpcb_track_kin<3, false, true>, a, lds);
-      } else if (n == 0) rc = launch_kernel(h, stream, mpcb_track_kin<0>, a, lds);
-      else if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin<1>, a, lds);
-      else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin<3>, a, lds);
-      else if (n <= 5) rc = launch_kernel(h, stream, mpcb_track_kin<5>, a, lds);
-      else rc = launch_kernel(h, stream, mpcb_track_kin<8>, a, lds);
-    } else if (h->cfg.model == MPCB_MODEL_DYN) {
-      if (n <= 1) rc = launch_kernel(h, stream, mpcb_kernel_dyn<1>, a, lds);
-      else if (n <= 3) rc = launch_kernel(h, stream, mpcb_kernel_dyn<3>, a, lds);
-      else if (n <= 5) rc = launch_kernel(h, stream, mpcb_kernel_dyn<5>, a, lds);
-      else rc = launch_kernel(h, stream, mpcb_kernel_dyn<8>, a, lds);
-    } else if (h->cfg.obs_mode == MPCB_OBS_DCBF && h->cfg.gamma < 1.0 - 1e-12 && n > 0) {   // general-gamma CBF rows
-      if (n == 1) rc = launch_kernel(h, stream, mpcb_kernel_kin<1, true>, a, lds);
-      else if (n <= 3) rc = launch_kernel(h, stream, mpcb_kernel_kin<3, true>, a, lds);
-      else rc = launch_kernel(h, stream, mpcb_kernel_kin<8, true>, a, lds);
-    } else if (is_rk4(h->cfg)) {                                                               // Runge-Kutta shooting rows
-      if (n == 0) rc = launch_kernel(h, stream, mpcb_kernel_kin<0, false, true>, a, lds);
-      else if (n == 1) rc = launch_kernel(h, stream, mpcb_kernel_kin<1, false, true>, a, lds);
-      else rc = launch_kernel(h, stream, mpcb_kernel_kin<3, false, true>, a, lds);
-    } else if (n == 0) rc = launch_kernel(h, stream, mpcb_kernel_kin<0>, a, lds);
-    else if (n == 1) rc = launch_kernel(h, stream, mpcb_kernel_kin<1>, a, lds);
-    else if (n <= 3) rc = launch_kernel(h, stream, mpcb_kernel_kin<3>, a, lds);
-    else if (n <= 5) rc = launch_kernel(h, stream, mpcb_kernel_kin<5>, a, lds);
-    else rc = launch_kernel(h, stream, mpcb_kernel_kin<8>, a, lds);
+  // the lean kernel over the whole grid, or the restoration-pass kernel: instances that ended the pass before it with
+  // MPCB_ST_NEEDS_RESTO continue, the others return
+  for (int i = 0; i < plan.n; ++i) {
+    a.pass = plan.pass[i];
+    const bool resto = a.pass == MPCB_PASS_RESTO;
+    int rc = mpcbd::visit(v, resto, [&](auto inst) { return launch_kernel(h, stream, kernel_of(inst), a, lds[resto]); });
     if (rc != MPCB_OK) return rc;
     HIP_TRY(h, hipGetLastError());
-    return MPCB_OK;
-  };
-  auto resto_pass = [&]() -> int {                // the restoration-pass kernel: instances that ended the pass before it with MPCB_ST_NEEDS_RESTO continue, the others return
-    a.pass = MPCB_PASS_RESTO;
-    const bool dyn = h->cfg.model == MPCB_MODEL_DYN;
-    const size_t lds2 = (size_t)(dyn ? mpcbk::layout_dyn(h->cfg.N, true, mpcbk::obs_in_lds(mpcbk::obs_capacity_dyn(n))).total
-                                     : mpcbk::layout_kin(h->cfg.N, h->nz, true, mpcbk::obs_in_lds(mpcbk::obs_capacity_kin(n, is_gen(h->cfg))), wide_table(h->cfg), trk).total) * sizeof(double);
-    if (lds2 > 160 * 1024) return fail(h, MPCB_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", lds2);
-    const bool gen = h->cfg.obs_mode == MPCB_OBS_DCBF && h->cfg.gamma < 1.0 - 1e-12 && n > 0;
-    if (prm) rc = launch_param_kernel(h, stream, a, lds2, true);
-    else if (trk) {
-      if (gen) {
-        if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin_resto<1, true>, a, lds2);
-        else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin_resto<3, true>, a, lds2);
-        else rc = launch_kernel(h, stream, mpcb_track_kin_resto<8, true>, a, lds2);
-      } else if (is_rk4(h->cfg)) {
-        if (n == 0) rc = launch_kernel(h, stream, mpcb_track_kin_resto<0, false, true>, a, lds2);
-        else if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin_resto<1, false, true>, a, lds2);
-        else rc = launch_kernel(h, stream, mpcb_track_kin_resto<3, false, true>, a, lds2);
-      } else if (n == 0) rc = launch_kernel(h, stream, mpcb_track_kin_resto<0>, a, lds2);
-      else if (n == 1) rc = launch_kernel(h, stream, mpcb_track_kin_resto<1>, a, lds2);
-      else if (n <= 3) rc = launch_kernel(h, stream, mpcb_track_kin_resto<3>, a, lds2);
-      else if (n <= 5) rc = launch_kernel(h, stream, mpcb_track_kin_resto<5>, a, lds2);
-      else rc = launch_kernel(h, stream, mpcb_track_kin_resto<8>, a, lds2);
-    } else if (dyn) {
-      if (n <= 1) rc = launch_kernel(h, stream, mpcb_kernel_dyn_resto<1>, a, lds2);
-      else if (n <= 3) rc = launch_kernel(h, stream, mpcb_kernel_dyn_resto<3>, a, lds2);
-      else if (n <= 5) rc = launch_kernel(h, stream, mpcb_kernel_dyn_resto<5>, a, lds2);
-      else rc = launch_kernel(h, stream, mpcb_kernel_dyn_resto<8>, a, lds2);
-    } else if (gen) {
-      if (n == 1) rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<1, true>, a, lds2);
-      else if (n <= 3) rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<3, true>, a, lds2);
-      else rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<8, true>, a, lds2);
-    } else if (is_rk4(h->cfg)) {
-      if (n == 0) rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<0, false, true>, a, lds2);
-      else if (n == 1) rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<1, false, true>, a, lds2);
-      else rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<3, false, true>, a, lds2);
-    } else if (n == 0) rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<0>, a, lds2);
-    else if (n == 1) rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<1>, a, lds2);
-    else if (n <= 3) rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<3>, a, lds2);
-    else if (n <= 5) rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<5>, a, lds2);
-    else rc = launch_kernel(h, stream, mpcb_kernel_kin_resto<8>, a, lds2);
-    if (rc != MPCB_OK) return rc;
-    HIP_TRY(h, hipGetLastError());
-    return MPCB_OK;
-  };
-  // first attempt from the caller's start, its restoration pass; with a second start (cfg.second_start after a roll-out start) the
-  // lean kernel once more over the same grid, where only the instances whose first attempt did not succeed run from z = 0, and the
-  // restoration pass of that attempt
-  const int ss = second_mode(h->cfg, a.z0);
-  rc = lean_pass(MPCB_PASS_FIRST);
-  // (second start of kind 1: the first attempt's restoration pass is skipped — its instances go straight to the second start)
-  if (rc == MPCB_OK && h->cfg.restoration && !(second_pass(h->cfg) && ss == 1)) rc = resto_pass();
-  if (rc == MPCB_OK && second_pass(h->cfg)) {
-    // (kind 1 on an instantiation that fuses: the second attempt ran inside the first launch)
-    const bool fused = ss == 1 && (h->cfg.model == MPCB_MODEL_DYN
-                                       ? ((n <= 1 && mpcb_dyn_fuses<1>) || (n > 1 && n <= 3 && mpcb_dyn_fuses<3>))
-                                       : (!is_gen(h->cfg) && !is_rk4(h->cfg) && ((n == 0 && mpcb_kin_fuses<0, false, false>) || (n == 1 && mpcb_kin_fuses<1, false, false>) ||
-                                                                                   (n > 1 && n <= 3 && mpcb_kin_fuses<3, false, false>))));
-    if (!fused) rc = lean_pass(MPCB_PASS_SECOND);
-    if (rc == MPCB_OK && h->cfg.restoration) rc = resto_pass();
   }
-  if (rc != MPCB_OK) return rc;
   HIP_TRY(h, hipEventRecord(evp.second, stream));
   h->ev_head = (h->ev_head + 1) % mpcb_handle::EV_RING; ++h->ev_pending;
   if (lane_id > 0) { HIP_TRY(h, hipEventRecord(L.done, stream)); L.busy = true; }
   return MPCB_OK;
-}
-
-// Launches of the per-instance kernels (mpcb_param_*, mpcb_advance_params).  Behind launch_solve, reached through the declaration in front
-// of it: templates are emitted in the order of their first use, and this keeps the new kernels behind the existing solve kernels in the
-// code object, whose layout then starts as it did before them.
-int launch_param_kernel(mpcb_handle* h, hipStream_t stream, const MpcbKArgs& a, size_t lds, bool resto) {
-  const int n = h->cfg.n_obs;
-  if (h->cfg.model == MPCB_MODEL_DYN) {
-    if (n <= 1) return resto ? launch_kernel(h, stream, mpcb_param_dyn_resto<1>, a, lds) : launch_kernel(h, stream, mpcb_param_dyn<1>, a, lds);
-    return resto ? launch_kernel(h, stream, mpcb_param_dyn_resto<3>, a, lds) : launch_kernel(h, stream, mpcb_param_dyn<3>, a, lds);
-  }
-  if (n == 0) return resto ? launch_kernel(h, stream, mpcb_param_kin_resto<0>, a, lds) : launch_kernel(h, stream, mpcb_param_kin<0>, a, lds);
-  if (n == 1) return resto ? launch_kernel(h, stream, mpcb_param_kin_resto<1>, a, lds) : launch_kernel(h, stream, mpcb_param_kin<1>, a, lds);
-  return resto ? launch_kernel(h, stream, mpcb_param_kin_resto<3>, a, lds) : launch_kernel(h, stream, mpcb_param_kin<3>, a, lds);
 }
 
 void launch_advance_params(int nx, hipStream_t s, const mpcb_config* d_cfgs, int B, int nz, const double* z, double* x0, double* z0, double* obs,
@@ -853,7 +741,8 @@ void launch_advance_params(int nx, hipStream_t s, const mpcb_config* d_cfgs, int
 
 // what the tracking entry points support: the kinematic model on a single-device handle
 int check_track(mpcb_handle* h) {
-  if (h->cfg.model != MPCB_MODEL_KIN) return fail(h, MPCB_E_UNSUPPORTED, "per-stage reference tracking is built for the kinematic model only");
+  mpcbd::Variant v;
+  { int rc = variant_or_fail(h, h->cfg, true, false, &v); if (rc != MPCB_OK) return rc; }
   if (!h->peers.empty()) return fail(h, MPCB_E_UNSUPPORTED, "per-stage reference tracking does not run on a device group (mpcb_set_devices)");
   return MPCB_OK;
 }
@@ -874,21 +763,40 @@ struct Carve {
   size_t bytes() const { return off + 256; }
 };
 
+// The pointers of one solve in the order every C entry lists them: device pointers for solve_on_device, the caller's host pointers in
+// HostSolve.  st_stride: stride of status / iters (a column of the closed loop's histories).  xref: [B, N, 4] per-stage reference, NULL = the
+// set-point solve.  cfgs: [B] per-instance configs on the device, NULL = the handle's config.
+struct SolveArgs {
+  int32_t B = 0; const double *x0 = nullptr, *xs = nullptr, *obs = nullptr; int32_t obs_kind = MPCB_OBSIN_STATIC; const double* z0 = nullptr;
+  double *z = nullptr, *obj = nullptr; int32_t *status = nullptr, *iters = nullptr; double *kkt = nullptr, *lam_g = nullptr, *lam_x = nullptr;
+  int32_t st_stride = 1; const double* xref = nullptr; const mpcb_config* cfgs = nullptr;
+};
+SolveArgs solve_args(int32_t B, const double* x0, const double* xs, const double* obs, int32_t obs_kind, const double* z0, double* z, double* obj,
+                     int32_t* status, int32_t* iters, double* kkt, double* lam_g, double* lam_x) {
+  SolveArgs s;
+  s.B = B; s.x0 = x0; s.xs = xs; s.obs = obs; s.obs_kind = obs_kind; s.z0 = z0; s.z = z; s.obj = obj; s.status = status; s.iters = iters;
+  s.kkt = kkt; s.lam_g = lam_g; s.lam_x = lam_x;
+  return s;
+}
+
+// what every solve entry checks first (B_checked: mpcb_solve_params has compared B with the set already and words it so)
+int check_solve_args(mpcb_handle* h, const SolveArgs& s, bool B_checked = false) {
+  if (s.B < 0 || !s.x0 || !s.xs || !s.z) return fail(h, MPCB_E_INVALID, B_checked ? "a required pointer is NULL" : "B < 0 or a required pointer is NULL");
+  if (h->cfg.n_obs > 0 && !s.obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
+  if (s.obs_kind != MPCB_OBSIN_STATIC && s.obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", s.obs_kind);
+  return MPCB_OK;
+}
+
 // one launch of the solve over B instances, everything resident on the handle's device, asynchronous on its stream
-int solve_on_device(mpcb_handle* h, int32_t B, const double* d_x0, const double* d_xs, const double* d_obs, int32_t obs_kind,
-                    const double* d_z0, double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, int32_t st_stride,
-                    double* d_kkt, double* d_lam_g, double* d_lam_x, int lane_id = 0, const double* d_xref = nullptr,
-                    const mpcb_config* d_cfgs = nullptr) {
-  if (B < 0 || !d_x0 || !d_xs || !d_z) return fail(h, MPCB_E_INVALID, "B < 0 or a required pointer is NULL");
-  if (h->cfg.n_obs > 0 && !d_obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
-  if (obs_kind != MPCB_OBSIN_STATIC && obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", obs_kind);
+int solve_on_device(mpcb_handle* h, const SolveArgs& s, int lane_id = 0) {
+  { int rc = check_solve_args(h, s); if (rc != MPCB_OK) return rc; }
   HIP_TRY(h, hipSetDevice(h->device));
   MpcbKArgs a;
-  a.cfg = h->cfg; a.B = B; a.nz = h->nz; a.ng = h->ng; a.obs_kind = obs_kind;
-  a.want_mult = (d_lam_g || d_lam_x) ? 1 : 0; a.trace_instance = -1; a.trace = nullptr; a.st_stride = st_stride; a.tgrid = h->d_tgrid;
-  a.x0 = d_x0; a.xs = d_xs; a.obs = d_obs; a.z0 = d_z0;
-  a.z = d_z; a.obj = d_obj; a.kkt = d_kkt; a.lam_g = d_lam_g; a.lam_x = d_lam_x; a.status = d_status; a.iters = d_iters;
-  a.xref = d_xref; a.cfgs = d_cfgs;
+  a.cfg = h->cfg; a.B = s.B; a.nz = h->nz; a.ng = h->ng; a.obs_kind = s.obs_kind;
+  a.want_mult = (s.lam_g || s.lam_x) ? 1 : 0; a.trace_instance = -1; a.trace = nullptr; a.st_stride = s.st_stride; a.tgrid = h->d_tgrid;
+  a.x0 = s.x0; a.xs = s.xs; a.obs = s.obs; a.z0 = s.z0;
+  a.z = s.z; a.obj = s.obj; a.kkt = s.kkt; a.lam_g = s.lam_g; a.lam_x = s.lam_x; a.status = s.status; a.iters = s.iters;
+  a.xref = s.xref; a.cfgs = s.cfgs;
   return launch_solve(h, a, lane_id);
 }
 
@@ -897,13 +805,13 @@ int solve_on_device(mpcb_handle* h, int32_t B, const double* d_x0, const double*
 // share a lane and are ordered.  Measured alternatives (C2, 4096 instances, MI355X): cutting every call into K chunks, chunk c on
 // lane c: 1.11 M solves/s against 1.48 M (only one batch's worth of workgroups is ever queued); cutting a lone synchronous call
 // into chunks: 5.5 ms per call against 4.2 ms for the single launch — so the host-pointer entries stay one launch on lane 0.
-int solve_next_lane(mpcb_handle* h, int32_t B, const double* d_x0, const double* d_xs, const double* d_obs, int32_t obs_kind,
-                    const double* d_z0, double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt,
-                    double* d_lam_g, double* d_lam_x, const double* d_xref = nullptr, const mpcb_config* d_cfgs = nullptr) {
+int solve_next_lane(mpcb_handle* h, const SolveArgs& s, int32_t sync) {
   const int K = h->lanes.empty() ? 1 : (int)h->lanes.size();
   const int lane = K == 1 ? 0 : h->next_lane;
   if (K > 1) h->next_lane = (h->next_lane + 1) % K;
-  return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, 1, d_kkt, d_lam_g, d_lam_x, lane, d_xref, d_cfgs);
+  int rc = solve_on_device(h, s, lane);
+  if (rc != MPCB_OK) return rc;
+  return sync ? mpcb_sync(h) : MPCB_OK;
 }
 
 // ---- parameter sets: validation on the host --------------------------------------------------------------------------------------
@@ -927,12 +835,7 @@ const char* structural_diff(const mpcb_config& r, const mpcb_config& c) {
 }
 
 // what the PARAMS kernels are built for, as far as the config says it
-int check_params_config(mpcb_handle* h, const mpcb_config& c) {
-  if (is_gen(c)) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets: general-gamma discrete-CBF rows have no per-instance kernel (keep-out or gamma = 1 rows only)");
-  if (c.integrator == MPCB_INT_RK4) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets: MPCB_INT_RK4 has no per-instance kernel (MPCB_INT_EULER only)");
-  if (c.n_obs > 3) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets: n_obs = %d, the per-instance kernels are built for up to 3 obstacles", c.n_obs);
-  return MPCB_OK;
-}
+int check_params_config(mpcb_handle* h, const mpcb_config& c) { mpcbd::Variant v; return variant_or_fail(h, c, false, true, &v); }
 
 // every row passes check_cfg and is structurally equal to `base`; the index of the first row that is not goes to *first_bad
 int check_params_rows(mpcb_handle* h, const mpcb_config& base, const mpcb_config* cfgs, int32_t B, int32_t* first_bad) {
@@ -1167,10 +1070,7 @@ int mpcb_solve_device(mpcb_handle* h, int32_t B, const double* d_x0, const doubl
                       const double* d_z0, double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt,
                       double* d_lam_g, double* d_lam_x, int32_t sync) {
   if (!h) return MPCB_E_INVALID;
-  int rc = solve_next_lane(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, d_kkt, d_lam_g, d_lam_x);
-  if (rc != MPCB_OK) return rc;
-  if (sync) return mpcb_sync(h);
-  return MPCB_OK;
+  return solve_next_lane(h, solve_args(B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, d_kkt, d_lam_g, d_lam_x), sync);
 }
 
 int mpcb_solve_device_ref(mpcb_handle* h, int32_t B, const double* d_x0, const double* d_xs, const double* d_x_ref, const double* d_obs,
@@ -1178,10 +1078,9 @@ int mpcb_solve_device_ref(mpcb_handle* h, int32_t B, const double* d_x0, const d
                           double* d_lam_g, double* d_lam_x, int32_t sync) {
   if (!h) return MPCB_E_INVALID;
   if (d_x_ref) { int rc = check_track(h); if (rc != MPCB_OK) return rc; }
-  int rc = solve_next_lane(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, d_kkt, d_lam_g, d_lam_x, d_x_ref);
-  if (rc != MPCB_OK) return rc;
-  if (sync) return mpcb_sync(h);
-  return MPCB_OK;
+  SolveArgs s = solve_args(B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, d_kkt, d_lam_g, d_lam_x);
+  s.xref = d_x_ref;
+  return solve_next_lane(h, s, sync);
 }
 
 int mpcb_set_inflight(mpcb_handle* h, int32_t k) {
@@ -1200,61 +1099,62 @@ namespace {
 // One host-pointer solve on one device, in two halves so that a device group can issue every shard before it waits for any:
 // issue() uploads the inputs and launches the solve (asynchronous on the handle's stream), collect() queues the downloads.
 struct HostSolve {
-  mpcb_handle* h; int32_t B; int obs_kind;
-  const double *x0, *xs, *obs, *z0; double *z, *obj, *kkt, *lam_g, *lam_x; int32_t *status, *iters;
-  double *d_x0, *d_xs, *d_obs, *d_z0, *d_z, *d_obj, *d_kkt, *d_lg, *d_lx; int32_t *d_st, *d_it;
-  const double* xref = nullptr; double* d_xr = nullptr;        // [B, N, 4] per-stage reference (mpcb_solve_ref), NULL = the set-point solve
-  const mpcb_config* d_cfgs = nullptr;                         // [B] per-instance configs on the device (mpcb_solve_params), NULL = the handle's config
+  mpcb_handle* h = nullptr;
+  SolveArgs in;        // the caller's host pointers (in.cfgs: the parameter set's rows, on the device already)
+  SolveArgs d;         // their device copies in the handle's scratch buffer
   int issue() {
     HIP_TRY(h, hipSetDevice(h->device));
     { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
     const int nx = h->nx, nz = h->nz, ng = h->ng, N = h->cfg.N;
-    const size_t n_obs_d = (size_t)B * h->cfg.n_obs * 6 * (obs_kind == MPCB_OBSIN_PREDICTED ? N + 1 : 1);
+    const int32_t B = in.B;
+    const size_t n_obs_d = (size_t)B * h->cfg.n_obs * 6 * (in.obs_kind == MPCB_OBSIN_PREDICTED ? N + 1 : 1);
+    double *d_x0, *d_xs, *d_obs, *d_z0, *d_xr;
     auto carve = [&](Carve& cv) {
       d_x0 = cv.take<double>((size_t)B * nx);
       d_xs = cv.take<double>((size_t)B * nx);
       d_obs = n_obs_d ? cv.take<double>(n_obs_d) : nullptr;
-      d_z0 = z0 ? cv.take<double>((size_t)B * nz) : nullptr;
-      d_z = cv.take<double>((size_t)B * nz);
-      d_obj = cv.take<double>(B);
-      d_kkt = cv.take<double>((size_t)B * 4);
-      d_lg = lam_g ? cv.take<double>((size_t)B * ng) : nullptr;
-      d_lx = lam_x ? cv.take<double>((size_t)B * nz) : nullptr;
-      d_st = cv.take<int32_t>(B);
-      d_it = cv.take<int32_t>(B);
-      d_xr = xref ? cv.take<double>((size_t)B * N * 4) : nullptr;
+      d_z0 = in.z0 ? cv.take<double>((size_t)B * nz) : nullptr;
+      d.z = cv.take<double>((size_t)B * nz);
+      d.obj = cv.take<double>(B);
+      d.kkt = cv.take<double>((size_t)B * 4);
+      d.lam_g = in.lam_g ? cv.take<double>((size_t)B * ng) : nullptr;
+      d.lam_x = in.lam_x ? cv.take<double>((size_t)B * nz) : nullptr;
+      d.status = cv.take<int32_t>(B);
+      d.iters = cv.take<int32_t>(B);
+      d_xr = in.xref ? cv.take<double>((size_t)B * N * 4) : nullptr;
     };
     { Carve dry{nullptr}; carve(dry); int rc = ensure_scratch(h, dry.bytes()); if (rc != MPCB_OK) return rc; }
     { Carve cv{(char*)h->d_buf}; carve(cv); }
+    d.B = B; d.obs_kind = in.obs_kind; d.x0 = d_x0; d.xs = d_xs; d.obs = d_obs; d.z0 = d_z0; d.xref = d_xr; d.cfgs = in.cfgs;
     hipStream_t s = h->stream;
-    if (d_xr) HIP_TRY(h, hipMemcpyAsync(d_xr, xref, (size_t)B * N * 4 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_x0, x0, (size_t)B * nx * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d_xs, xs, (size_t)B * nx * 8, hipMemcpyHostToDevice, s));
-    if (d_obs) HIP_TRY(h, hipMemcpyAsync(d_obs, obs, n_obs_d * 8, hipMemcpyHostToDevice, s));
-    if (d_z0) HIP_TRY(h, hipMemcpyAsync(d_z0, z0, (size_t)B * nz * 8, hipMemcpyHostToDevice, s));
-    return solve_on_device(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_st, d_it, 1, d_kkt, d_lg, d_lx, 0, d_xr, d_cfgs);
+    if (d_xr) HIP_TRY(h, hipMemcpyAsync(d_xr, in.xref, (size_t)B * N * 4 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d_x0, in.x0, (size_t)B * nx * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(d_xs, in.xs, (size_t)B * nx * 8, hipMemcpyHostToDevice, s));
+    if (d_obs) HIP_TRY(h, hipMemcpyAsync(d_obs, in.obs, n_obs_d * 8, hipMemcpyHostToDevice, s));
+    if (d_z0) HIP_TRY(h, hipMemcpyAsync(d_z0, in.z0, (size_t)B * nz * 8, hipMemcpyHostToDevice, s));
+    return solve_on_device(h, d);
   }
   int collect() {
     HIP_TRY(h, hipSetDevice(h->device));
     { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
-    const int nz = h->nz, ng = h->ng;
+    const size_t B = (size_t)in.B, nz = h->nz, ng = h->ng;
     hipStream_t s = h->stream;
-    if (z) HIP_TRY(h, hipMemcpyAsync(z, d_z, (size_t)B * nz * 8, hipMemcpyDeviceToHost, s));
-    if (obj) HIP_TRY(h, hipMemcpyAsync(obj, d_obj, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    if (kkt) HIP_TRY(h, hipMemcpyAsync(kkt, d_kkt, (size_t)B * 4 * 8, hipMemcpyDeviceToHost, s));
-    if (status) HIP_TRY(h, hipMemcpyAsync(status, d_st, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    if (iters) HIP_TRY(h, hipMemcpyAsync(iters, d_it, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    if (lam_g) HIP_TRY(h, hipMemcpyAsync(lam_g, d_lg, (size_t)B * ng * 8, hipMemcpyDeviceToHost, s));
-    if (lam_x) HIP_TRY(h, hipMemcpyAsync(lam_x, d_lx, (size_t)B * nz * 8, hipMemcpyDeviceToHost, s));
+    if (in.z) HIP_TRY(h, hipMemcpyAsync(in.z, d.z, B * nz * 8, hipMemcpyDeviceToHost, s));
+    if (in.obj) HIP_TRY(h, hipMemcpyAsync(in.obj, d.obj, B * 8, hipMemcpyDeviceToHost, s));
+    if (in.kkt) HIP_TRY(h, hipMemcpyAsync(in.kkt, d.kkt, B * 4 * 8, hipMemcpyDeviceToHost, s));
+    if (in.status) HIP_TRY(h, hipMemcpyAsync(in.status, d.status, B * 4, hipMemcpyDeviceToHost, s));
+    if (in.iters) HIP_TRY(h, hipMemcpyAsync(in.iters, d.iters, B * 4, hipMemcpyDeviceToHost, s));
+    if (in.lam_g) HIP_TRY(h, hipMemcpyAsync(in.lam_g, d.lam_g, B * ng * 8, hipMemcpyDeviceToHost, s));
+    if (in.lam_x) HIP_TRY(h, hipMemcpyAsync(in.lam_x, d.lam_x, B * nz * 8, hipMemcpyDeviceToHost, s));
     return MPCB_OK;
   }
 };
 
 // mpcb_solve on a device group (mpcb_set_devices): contiguous shards, no data-path collective, one all-gather of z
-int solve_group(mpcb_handle* h, int32_t B, const double* x0, const double* xs, const double* obs, int32_t obs_kind, const double* z0,
-                double* z, double* obj, int32_t* status, int32_t* iters, double* kkt, double* lam_g, double* lam_x) {
+int solve_group(mpcb_handle* h, const SolveArgs& in) {
   const int G = (int)h->peers.size(), nx = h->nx, nz = h->nz, ng = h->ng, N = h->cfg.N;
-  const size_t obs_row = (size_t)h->cfg.n_obs * 6 * (obs_kind == MPCB_OBSIN_PREDICTED ? N + 1 : 1);
+  const int32_t B = in.B;
+  const size_t obs_row = (size_t)h->cfg.n_obs * 6 * (in.obs_kind == MPCB_OBSIN_PREDICTED ? N + 1 : 1);
   const Rccl* R = rccl();
   std::vector<HostSolve> part(G);
   int64_t longest = 0;
@@ -1265,11 +1165,11 @@ int solve_group(mpcb_handle* h, int32_t B, const double* x0, const double* xs, c
     p->cfg = h->cfg;                                       // (bounds reach the peers in mpcb_set_bounds, the time grid in mpcb_set_time_grid / mpcb_set_devices; this keeps option edits of the leader in step)
     HostSolve& q = part[g];
     q = HostSolve{};
-    q.h = p; q.B = (int32_t)(hi - lo); q.obs_kind = obs_kind;
-    q.x0 = x0 + lo * nx; q.xs = xs + lo * nx; q.obs = obs ? obs + lo * obs_row : nullptr; q.z0 = z0 ? z0 + lo * nz : nullptr;
-    q.z = nullptr;                                         // z comes back from the gathered copy
-    q.obj = obj ? obj + lo : nullptr; q.kkt = kkt ? kkt + lo * 4 : nullptr; q.status = status ? status + lo : nullptr;
-    q.iters = iters ? iters + lo : nullptr; q.lam_g = lam_g ? lam_g + lo * ng : nullptr; q.lam_x = lam_x ? lam_x + lo * nz : nullptr;
+    q.h = p;                                               // rows lo..hi of every array; z comes back from the gathered copy
+    q.in = solve_args((int32_t)(hi - lo), in.x0 + lo * nx, in.xs + lo * nx, in.obs ? in.obs + lo * obs_row : nullptr, in.obs_kind,
+                      in.z0 ? in.z0 + lo * nz : nullptr, nullptr, in.obj ? in.obj + lo : nullptr, in.status ? in.status + lo : nullptr,
+                      in.iters ? in.iters + lo : nullptr, in.kkt ? in.kkt + lo * 4 : nullptr, in.lam_g ? in.lam_g + lo * ng : nullptr,
+                      in.lam_x ? in.lam_x + lo * nz : nullptr);
     // all-gather target and a padded send block (shards may differ by one row) on this device
     HIP_TRY(p, hipSetDevice(p->device));
     const size_t need = (size_t)(G + 1) * longest * nz;
@@ -1288,10 +1188,10 @@ int solve_group(mpcb_handle* h, int32_t B, const double* x0, const double* xs, c
       mpcb_handle* p = h->peers[g]; HostSolve& q = part[g];
       auto body = [&]() -> int {
         HIP_TRY(p, hipSetDevice(p->device));
-        if (q.B > 0) { int rc = q.issue(); if (rc != MPCB_OK) return rc; }
+        if (q.in.B > 0) { int rc = q.issue(); if (rc != MPCB_OK) return rc; }
         double* send = p->d_gather + (size_t)G * longest * nz;
-        if (q.B < longest) HIP_TRY(p, hipMemsetAsync(send, 0, (size_t)longest * nz * 8, p->stream));
-        if (q.B > 0) HIP_TRY(p, hipMemcpyAsync(send, q.d_z, (size_t)q.B * nz * 8, hipMemcpyDeviceToDevice, p->stream));
+        if (q.in.B < longest) HIP_TRY(p, hipMemsetAsync(send, 0, (size_t)longest * nz * 8, p->stream));
+        if (q.in.B > 0) HIP_TRY(p, hipMemcpyAsync(send, q.d.z, (size_t)q.in.B * nz * 8, hipMemcpyDeviceToDevice, p->stream));
         return MPCB_OK;
       };
       rcs[g] = body();
@@ -1312,7 +1212,7 @@ int solve_group(mpcb_handle* h, int32_t B, const double* x0, const double* xs, c
   NCCL_TRY(h, R, R->GroupEnd());
   for (int g = 0; g < G; ++g) {
     mpcb_handle* p = h->peers[g];
-    if (part[g].B > 0) { int rc = part[g].collect(); if (rc != MPCB_OK) return fail(h, rc, "device %d: %s", p->device, p->err.c_str()); }
+    if (part[g].in.B > 0) { int rc = part[g].collect(); if (rc != MPCB_OK) return fail(h, rc, "device %d: %s", p->device, p->err.c_str()); }
     p->gathered_rows = (size_t)longest; p->gathered_B = B;
   }
   // the caller's z: the gathered copy of device 0, shard blocks de-padded
@@ -1320,7 +1220,7 @@ int solve_group(mpcb_handle* h, int32_t B, const double* x0, const double* xs, c
   HIP_TRY(p0, hipSetDevice(p0->device));
   for (int g = 0; g < G; ++g) {
     int64_t lo, hi; mpcb_shard_bounds(B, G, g, &lo, &hi);
-    if (hi > lo) HIP_TRY(p0, hipMemcpyAsync(z + lo * nz, p0->d_gather + (size_t)g * longest * nz, (size_t)(hi - lo) * nz * 8, hipMemcpyDeviceToHost, p0->stream));
+    if (hi > lo) HIP_TRY(p0, hipMemcpyAsync(in.z + lo * nz, p0->d_gather + (size_t)g * longest * nz, (size_t)(hi - lo) * nz * 8, hipMemcpyDeviceToHost, p0->stream));
   }
   for (int g = 0; g < G; ++g) { mpcb_handle* p = h->peers[g]; HIP_TRY(p, hipSetDevice(p->device)); HIP_TRY(p, hipStreamSynchronize(p->stream)); }
   HIP_TRY(h, hipSetDevice(h->device));
@@ -1331,17 +1231,13 @@ int solve_group(mpcb_handle* h, int32_t B, const double* x0, const double* xs, c
 
 extern "C" {
 
-int mpcb_solve(mpcb_handle* h, int32_t B, const double* x0, const double* xs, const double* obs, int32_t obs_kind, const double* z0,
-               double* z, double* obj, int32_t* status, int32_t* iters, double* kkt, double* lam_g, double* lam_x) {
-  if (!h) return MPCB_E_INVALID;
-  if (B < 0 || !x0 || !xs || !z) return fail(h, MPCB_E_INVALID, "B < 0 or a required pointer is NULL");
-  if (h->cfg.n_obs > 0 && !obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
-  if (obs_kind != MPCB_OBSIN_STATIC && obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", obs_kind);
-  if (B == 0) return MPCB_OK;
-  if (!h->peers.empty()) return solve_group(h, B, x0, xs, obs, obs_kind, z0, z, obj, status, iters, kkt, lam_g, lam_x);
-  HostSolve q{};
-  q.h = h; q.B = B; q.obs_kind = obs_kind; q.x0 = x0; q.xs = xs; q.obs = obs; q.z0 = z0;
-  q.z = z; q.obj = obj; q.kkt = kkt; q.lam_g = lam_g; q.lam_x = lam_x; q.status = status; q.iters = iters;
+// the host-pointer solves: checks, upload and launch, download, wait
+static int solve_host(mpcb_handle* h, const SolveArgs& in, bool B_checked = false) {
+  { int rc = check_solve_args(h, in, B_checked); if (rc != MPCB_OK) return rc; }
+  if (in.B == 0) return MPCB_OK;
+  if (!h->peers.empty()) return solve_group(h, in);            // (a reference or a parameter set has been refused on a group before this)
+  HostSolve q;
+  q.h = h; q.in = in;
   int rc = q.issue();
   if (rc != MPCB_OK) return rc;
   rc = q.collect();
@@ -1350,24 +1246,19 @@ int mpcb_solve(mpcb_handle* h, int32_t B, const double* x0, const double* xs, co
   return MPCB_OK;
 }
 
+int mpcb_solve(mpcb_handle* h, int32_t B, const double* x0, const double* xs, const double* obs, int32_t obs_kind, const double* z0,
+               double* z, double* obj, int32_t* status, int32_t* iters, double* kkt, double* lam_g, double* lam_x) {
+  if (!h) return MPCB_E_INVALID;
+  return solve_host(h, solve_args(B, x0, xs, obs, obs_kind, z0, z, obj, status, iters, kkt, lam_g, lam_x));
+}
+
 int mpcb_solve_ref(mpcb_handle* h, int32_t B, const double* x0, const double* xs, const double* x_ref, const double* obs, int32_t obs_kind,
                    const double* z0, double* z, double* obj, int32_t* status, int32_t* iters, double* kkt, double* lam_g, double* lam_x) {
   if (!h) return MPCB_E_INVALID;
-  if (!x_ref) return mpcb_solve(h, B, x0, xs, obs, obs_kind, z0, z, obj, status, iters, kkt, lam_g, lam_x);
-  { int rc = check_track(h); if (rc != MPCB_OK) return rc; }
-  if (B < 0 || !x0 || !xs || !z) return fail(h, MPCB_E_INVALID, "B < 0 or a required pointer is NULL");
-  if (h->cfg.n_obs > 0 && !obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
-  if (obs_kind != MPCB_OBSIN_STATIC && obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", obs_kind);
-  if (B == 0) return MPCB_OK;
-  HostSolve q{};
-  q.h = h; q.B = B; q.obs_kind = obs_kind; q.x0 = x0; q.xs = xs; q.obs = obs; q.z0 = z0; q.xref = x_ref;
-  q.z = z; q.obj = obj; q.kkt = kkt; q.lam_g = lam_g; q.lam_x = lam_x; q.status = status; q.iters = iters;
-  int rc = q.issue();
-  if (rc != MPCB_OK) return rc;
-  rc = q.collect();
-  if (rc != MPCB_OK) return rc;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return MPCB_OK;
+  if (x_ref) { int rc = check_track(h); if (rc != MPCB_OK) return rc; }
+  SolveArgs in = solve_args(B, x0, xs, obs, obs_kind, z0, z, obj, status, iters, kkt, lam_g, lam_x);
+  in.xref = x_ref;
+  return solve_host(h, in);
 }
 
 int mpcb_solve_trace(mpcb_handle* h, const double* x0, const double* xs, const double* obs, int32_t obs_kind, const double* z0,
@@ -1475,7 +1366,9 @@ static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const doub
       HIP_TRY(h, hipGetLastError());
     }
     // the solve kernel writes status / iters of step t straight into column t of the [B, steps] histories
-    int rc = solve_on_device(h, B, d_x0, d_xs, obs_in, kind, d_z0, d_z, nullptr, d_st + t, d_it + t, steps, nullptr, nullptr, nullptr, 0, d_xr, d_cfgs);
+    SolveArgs sv = solve_args(B, d_x0, d_xs, obs_in, kind, d_z0, d_z, nullptr, d_st + t, d_it + t, nullptr, nullptr, nullptr);
+    sv.st_stride = steps; sv.xref = d_xr; sv.cfgs = d_cfgs;
+    int rc = solve_on_device(h, sv);
     if (rc != MPCB_OK) return rc;
     if (d_cfgs)            // solve and plant step both from row b of the parameter set
       launch_advance_params(nx, s, d_cfgs, B, nz, d_z, d_x0, d_z0, d_obs, d_xh, d_uh, d_st + t, steps, t, steps, move, hold, Tstep);
@@ -1560,18 +1453,9 @@ int mpcb_solve_params(mpcb_handle* h, int32_t B, const mpcb_params* p, const dou
                       const double* z0, double* z, double* obj, int32_t* status, int32_t* iters, double* kkt, double* lam_g, double* lam_x) {
   if (!h) return MPCB_E_INVALID;
   { int rc = check_params_use(h, p, B); if (rc != MPCB_OK) return rc; }
-  if (!x0 || !xs || !z) return fail(h, MPCB_E_INVALID, "a required pointer is NULL");
-  if (h->cfg.n_obs > 0 && !obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
-  if (obs_kind != MPCB_OBSIN_STATIC && obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", obs_kind);
-  HostSolve q{};
-  q.h = h; q.B = B; q.obs_kind = obs_kind; q.x0 = x0; q.xs = xs; q.obs = obs; q.z0 = z0; q.d_cfgs = p->d_cfgs;
-  q.z = z; q.obj = obj; q.kkt = kkt; q.lam_g = lam_g; q.lam_x = lam_x; q.status = status; q.iters = iters;
-  int rc = q.issue();
-  if (rc != MPCB_OK) return rc;
-  rc = q.collect();
-  if (rc != MPCB_OK) return rc;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return MPCB_OK;
+  SolveArgs in = solve_args(B, x0, xs, obs, obs_kind, z0, z, obj, status, iters, kkt, lam_g, lam_x);
+  in.cfgs = p->d_cfgs;
+  return solve_host(h, in, true);
 }
 
 int mpcb_solve_device_params(mpcb_handle* h, int32_t B, const mpcb_params* p, const double* d_x0, const double* d_xs, const double* d_obs,
@@ -1579,10 +1463,9 @@ int mpcb_solve_device_params(mpcb_handle* h, int32_t B, const mpcb_params* p, co
                              double* d_lam_g, double* d_lam_x, int32_t sync) {
   if (!h) return MPCB_E_INVALID;
   { int rc = check_params_use(h, p, B); if (rc != MPCB_OK) return rc; }
-  int rc = solve_next_lane(h, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, d_kkt, d_lam_g, d_lam_x, nullptr, p->d_cfgs);
-  if (rc != MPCB_OK) return rc;
-  if (sync) return mpcb_sync(h);
-  return MPCB_OK;
+  SolveArgs s = solve_args(B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, d_obj, d_status, d_iters, d_kkt, d_lam_g, d_lam_x);
+  s.cfgs = p->d_cfgs;
+  return solve_next_lane(h, s, sync);
 }
 
 int mpcb_closed_loop_params(mpcb_handle* h, int32_t B, int32_t steps, const mpcb_params* p, const double* x0, const double* xs, double* obs_state,

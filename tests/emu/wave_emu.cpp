@@ -1,16 +1,20 @@
 // tests/emu/wave_emu.cpp — TEST INFRASTRUCTURE ONLY.
 //
-// Steps the device source mpc_motion_planning_amd/csrc/mpcb_kernel.h on the CPU: every lane of the wavefront is a
-// host thread, cross-lane primitives (mpcb_wave.h, MPCB_WAVE_EMU branch) go through a barrier.  It exists so that
-// the kernel's logic can be checked against the oracle in the `-m "not gpu"` suite and while developing without
-// a GPU.  It is NOT part of libmpcbatch.so, is never loaded by the mpc_motion_planning_amd package and is far
-// too slow to be a fallback (64 OS threads per instance).
+// Steps the device source mpc_motion_planning_amd/csrc/mpcb_kernel.h / mpcb_kernel_dyn.h on the CPU: every lane of the wavefront is a
+// host thread, cross-lane primitives (mpcb_wave.h, MPCB_WAVE_EMU branch) go through a barrier.  Which instantiation is stepped, with
+// how much LDS and in which order of passes is read from mpcb_dispatch.h, the header mpcb_api.hip launches by: plain, tracking (xref)
+// and per-instance (cfgs) solves alike.  It exists so that the kernels' logic can be checked against the oracle in the `-m "not gpu"`
+// suite and while developing without a GPU.  It is NOT part of libmpcbatch.so, is never loaded by the mpc_motion_planning_amd package
+// and is far too slow to be a fallback (64 OS threads per instance).
 #define MPCB_WAVE_EMU 1
 #include "../../mpc_motion_planning_amd/csrc/mpcb_kernel_dyn.h"
+#include "../../mpc_motion_planning_amd/csrc/mpcb_dispatch.h"
 
 #include <thread>
 #include <limits>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 namespace wv {
@@ -18,85 +22,115 @@ thread_local int t_lane = 0;
 thread_local Emu* t_emu = nullptr;
 }
 
-template <int NOBS>
-static void run_instance(const MpcbKArgs& a, int b) {
-  using namespace mpcbk;
-  const bool dyn = a.cfg.model == MPCB_MODEL_DYN;
-  const bool rp = a.pass == MPCB_PASS_RESTO;                      // restoration pass: the RESTO instantiations
-  const bool rk4 = !dyn && a.cfg.integrator == MPCB_INT_RK4;
-  const int total = dyn ? layout_dyn(a.cfg.N, rp, obs_in_lds(NOBS)).total : layout_kin(a.cfg.N, a.nz, rp, obs_in_lds(NOBS)).total;
-  // LDS starts as garbage on the device: poison it here (MPCB_EMU_LDS_FILL, default NaN), so that a read of a never-written slot shows
-  const char* fill_env = std::getenv("MPCB_EMU_LDS_FILL");
-  std::vector<double> lds(total + 64, fill_env ? std::atof(fill_env) : std::numeric_limits<double>::quiet_NaN());
-  std::barrier<> bar(64);
-  wv::Emu emu; emu.bar = &bar;
-  std::vector<std::thread> th;
-  for (int l = 0; l < 64; ++l)
-    th.emplace_back([&, l]() {
-      wv::t_lane = l; wv::t_emu = &emu;
-      const bool gen = !dyn && a.cfg.obs_mode == MPCB_OBS_DCBF && a.cfg.gamma < 1.0 - 1e-12 && NOBS > 0;   // as mpcb_api.hip dispatches
-      if (dyn && rp) mpcb_solve_dyn<NOBS, true>(a, b, lds.data(), a.pass);
-      else if (dyn) mpcb_solve_dyn<NOBS>(a, b, lds.data(), a.pass);
-      else if (gen && rp) mpcb_solve_kin<(NOBS > 0 ? NOBS : 1), true, true>(a, b, lds.data(), a.pass);
-      else if (gen) mpcb_solve_kin<(NOBS > 0 ? NOBS : 1), true>(a, b, lds.data(), a.pass);
-      else if (rk4 && rp) mpcb_solve_kin<(NOBS <= 3 ? NOBS : 3), false, true, true>(a, b, lds.data(), a.pass);
-      else if (rk4) mpcb_solve_kin<(NOBS <= 3 ? NOBS : 3), false, false, true>(a, b, lds.data(), a.pass);
-      else if (rp) mpcb_solve_kin<NOBS, false, true>(a, b, lds.data(), a.pass);
-      else mpcb_solve_kin<NOBS>(a, b, lds.data(), a.pass);
-    });
-  for (auto& t : th) t.join();
+constexpr int MPCB_EMU_E_GUARD = -100;      // a word behind the LDS the library allocates at launch was written
+constexpr int GUARD = 64;
+
+// the solve function an instantiation tag (mpcbd::Inst) stands for
+template <class T> static void solve_as(T, const MpcbKArgs& a, int b, double* lds, int pass) {
+  if constexpr (T::model == MPCB_MODEL_DYN) mpcb_solve_dyn<T::nobs, T::resto, T::params>(a, b, lds, pass);
+  else mpcb_solve_kin<T::nobs, T::gen, T::resto, T::rk4, T::track, T::params>(a, b, lds, pass);
 }
 
+// One workgroup of one launch: instance b from a.pass on; `fused`: the wrapper's loop of the instantiations that fuse (mpcb_api.hip) — an
+// instance whose first attempt fails starts its second at once, in the same LDS.  The LDS is exactly the doubles the library passes at
+// launch, and starts as garbage on the device: poisoned here (MPCB_EMU_LDS_FILL, default NaN), so that a read of a never-written slot
+// shows.  Behind it a guard of NaNs that nothing may write.
+static int run_instance(const mpcbd::Variant& v, bool fused, const MpcbKArgs& a, int b) {
+  const bool resto = a.pass == MPCB_PASS_RESTO;
+  const int total = mpcbd::lds_doubles(v, a.cfg.N, resto);
+  const char* fill_env = std::getenv("MPCB_EMU_LDS_FILL");
+  std::vector<double> lds(total + GUARD, std::numeric_limits<double>::quiet_NaN());
+  if (fill_env) std::fill(lds.begin(), lds.begin() + total, std::atof(fill_env));
+  std::barrier<> bar(64);
+  wv::Emu emu; emu.bar = &bar;
+  const int rc = mpcbd::visit(v, resto, [&](auto inst) {
+    std::vector<std::thread> th;
+    for (int l = 0; l < 64; ++l)
+      th.emplace_back([&, l]() {
+        wv::t_lane = l; wv::t_emu = &emu;
+        int pass = a.pass;
+        for (;;) {
+          solve_as(inst, a, b, lds.data(), pass);
+          if (!fused || pass != MPCB_PASS_FIRST || !mpcbd::second_kind1(a.cfg, a.z0 != nullptr)) break;
+          wv::sync();                                             // the status lane 0 has just stored
+          const int st = a.status[b];
+          wv::sync();
+          if (st == MPCB_ST_SOLVED || st == MPCB_ST_ACCEPTABLE || st == MPCB_ST_INFEASIBLE_X0) break;
+          pass = MPCB_PASS_SECOND;
+        }
+      });
+    for (auto& t : th) t.join();
+    return MPCB_OK;
+  });
+  if (rc != MPCB_OK) return rc;
+  for (int i = 0; i < GUARD; ++i)
+    if (lds[total + i] == lds[total + i]) {
+      std::fprintf(stderr, "mpcb_emu: write %d doubles behind the %d doubles of LDS (model %d, capacity %d, gen %d, rk4 %d, track %d, params %d, pass %d)\n",
+                   i, total, v.model, v.nobs, v.gen, v.rk4, v.track, v.params, a.pass);
+      return MPCB_EMU_E_GUARD;
+    }
+  return MPCB_OK;
+}
+
+// xref: [B, N, 4] per-stage reference, NULL = the set-point solve.  cfgs: [B] per-instance configs (instance b is solved under row b, cfg
+// plays the handle's config; the rows are NOT validated here, mpcb_params_check does that), NULL = cfg for every instance.
 extern "C" int mpcb_emu_solve(const mpcb_config* cfg, int32_t B, const double* x0, const double* xs, const double* obs,
                               int32_t obs_kind, const double* z0, double* z, double* obj, int32_t* status, int32_t* iters,
-                              double* kkt, double* lam_g, double* lam_x, double* trace, int32_t trace_instance, const double* tgrid) {
+                              double* kkt, double* lam_g, double* lam_x, double* trace, int32_t trace_instance, const double* tgrid,
+                              const double* xref, const mpcb_config* cfgs) {
   if (!cfg) return MPCB_E_INVALID;
+  mpcbd::Variant v;
+  { const mpcbd::Refusal r = mpcbd::variant_of(*cfg, xref != nullptr, cfgs != nullptr, &v); if (r.code != MPCB_OK) return r.code; }
+  const bool fused = mpcbd::fuses(v);
+  const mpcbd::Plan plan = mpcbd::pass_plan(*cfg, z0 != nullptr, fused);
   const int nx = cfg->model == MPCB_MODEL_DYN ? 6 : 4;
   int nrate = 0;
   for (int i = 0; i < 2; ++i) if (cfg->du_lo[i] > -1e300 || cfg->du_hi[i] < 1e300) ++nrate;
   MpcbKArgs a{};
   a.st_stride = 1;
-  a.cfg = *cfg; a.B = B; a.obs_kind = obs_kind; a.want_mult = (lam_g || lam_x) ? 1 : 0; a.trace_instance = trace_instance;
+  a.cfg = *cfg; a.cfgs = cfgs; a.B = B; a.obs_kind = obs_kind; a.want_mult = (lam_g || lam_x) ? 1 : 0; a.trace_instance = trace_instance;
   a.nz = 2 * cfg->N + nx * (cfg->N + 1);
   a.ng = nx * (cfg->N + 1) + nrate * (cfg->N - 1) + cfg->n_obs * (cfg->obs_terminal ? cfg->N + 1 : cfg->N);
   a.x0 = x0; a.xs = xs; a.obs = obs; a.z0 = z0; a.z = z; a.obj = obj; a.kkt = kkt; a.lam_g = lam_g; a.lam_x = lam_x;
-  a.status = status; a.iters = iters; a.trace = trace; a.tgrid = tgrid;
+  a.status = status; a.iters = iters; a.trace = trace; a.tgrid = tgrid; a.xref = xref;
   std::vector<double> work((size_t)B * mpcbk::WK_SIZE, 0.0);
-  // as mpcb_api.hip: first pass, second-start pass (cfg.second_start), restoration pass (cfg.restoration)
-  const bool second = cfg->second_start && cfg->init_rollout;
-  a.work = (cfg->restoration || second) ? work.data() : nullptr;
-  // launch order of mpcb_api.hip: first attempt, its restoration pass, second attempt, its restoration pass
-  const int order[4] = {MPCB_PASS_FIRST, MPCB_PASS_RESTO, MPCB_PASS_SECOND, MPCB_PASS_RESTO};
-  for (int q = 0; q < 4; ++q) {
-    const int pass = order[q];
-    if ((q >= 2 && !second) || (pass == MPCB_PASS_RESTO && !cfg->restoration)) continue;
-    const int ss = cfg->second_start == 3 ? (z0 ? 2 : 1) : cfg->second_start;   // 3: by the kind of start, as mpcb_api.hip
-    if (q == 1 && second && ss == 1) continue;      // second start instead of the first attempt's restoration
-    a.pass = pass;
-    for (int b = 0; b < B; ++b) {
-      if (pass == MPCB_PASS_SECOND && (status[b] == MPCB_ST_SOLVED || status[b] == MPCB_ST_ACCEPTABLE || status[b] == MPCB_ST_INFEASIBLE_X0)) continue;
-      if (pass == MPCB_PASS_RESTO && status[b] != MPCB_ST_NEEDS_RESTO) continue;
-      if (cfg->n_obs == 0) run_instance<0>(a, b);
-      else if (cfg->n_obs == 1) run_instance<1>(a, b);
-      else if (cfg->n_obs <= 3) run_instance<3>(a, b);
-      else if (cfg->n_obs <= 8) run_instance<8>(a, b);
-      else return MPCB_E_UNSUPPORTED;
+  a.work = mpcbd::multi_pass(*cfg) ? work.data() : nullptr;
+  for (int q = 0; q < plan.n; ++q) {
+    a.pass = plan.pass[q];
+    for (int b = 0; b < B; ++b) {      // (the workgroups that would return at once are not started)
+      if (a.pass == MPCB_PASS_SECOND && (status[b] == MPCB_ST_SOLVED || status[b] == MPCB_ST_ACCEPTABLE || status[b] == MPCB_ST_INFEASIBLE_X0)) continue;
+      if (a.pass == MPCB_PASS_RESTO && status[b] != MPCB_ST_NEEDS_RESTO) continue;
+      const int rc = run_instance(v, fused, a, b);
+      if (rc != MPCB_OK) return rc;
     }
   }
   return MPCB_OK;
 }
 
-// closed-form dyn model derivatives of the kernel source (host-compiled) for comparison with the oracle's AD
-// LDS bytes of one instance (= one workgroup) as the kernels lay it out: `pass` 0 first pass, 1 restoration pass; as mpcb_api.hip computes it
+// LDS bytes of one instance (= one workgroup) as the library sizes it at launch: `pass` 0 first pass, 1 restoration pass
 extern "C" int64_t mpcb_emu_lds_bytes(const mpcb_config* cfg, int32_t pass) {
-  using namespace mpcbk;
-  const int n = cfg->n_obs;
-  if (cfg->model == MPCB_MODEL_DYN) return (int64_t)layout_dyn(cfg->N, pass == 1, obs_in_lds(obs_capacity_dyn(n))).total * 8;
-  const bool gen = cfg->obs_mode == MPCB_OBS_DCBF && cfg->gamma < 1.0 - 1e-12 && n > 0;
-  const int nz = 2 * cfg->N + 4 * (cfg->N + 1);
-  return (int64_t)layout_kin(cfg->N, nz, pass == 1, obs_in_lds(obs_capacity_kin(n, gen)), gen).total * 8;
+  mpcbd::Variant v;
+  if (mpcbd::variant_of(*cfg, false, false, &v).code != MPCB_OK) return -1;
+  return (int64_t)mpcbd::lds_bytes(v, cfg->N, pass == 1);
 }
 
+// The policy of mpcb_dispatch.h for one solve, for tests/test_dispatch_cpu.py.  fused: 0 / 1 plan as if the instantiation did not / did
+// fuse, -1 as it does.  out[14]: model, capacity, gen, rk4, track, params, fuses, LDS bytes of the first and of the restoration pass,
+// number of passes, the passes.  Returns variant_of's code; `why` (256 bytes) takes its message.
+extern "C" int mpcb_emu_dispatch(const mpcb_config* cfg, int32_t track, int32_t params, int32_t start_given, int32_t fused, int64_t* out, char* why) {
+  mpcbd::Variant v;
+  const mpcbd::Refusal r = mpcbd::variant_of(*cfg, track != 0, params != 0, &v);
+  std::snprintf(why, 256, r.fmt, cfg->n_obs);
+  if (r.code != MPCB_OK) return r.code;
+  const mpcbd::Plan plan = mpcbd::pass_plan(*cfg, start_given != 0, fused < 0 ? mpcbd::fuses(v) : fused != 0);
+  const int64_t head[10] = {v.model, v.nobs, v.gen, v.rk4, v.track, v.params, mpcbd::fuses(v), (int64_t)mpcbd::lds_bytes(v, cfg->N, false),
+                            (int64_t)mpcbd::lds_bytes(v, cfg->N, true), plan.n};
+  for (int i = 0; i < 10; ++i) out[i] = head[i];
+  for (int i = 0; i < 4; ++i) out[10 + i] = i < plan.n ? plan.pass[i] : -1;
+  return MPCB_OK;
+}
+
+// closed-form dyn model derivatives of the kernel source (host-compiled) for comparison with the oracle's AD
 extern "C" int mpcb_emu_dyn_model(const mpcb_config* cfg, const double* X, const double* U, const double* lam, double* F, double* jac16,
                                   double* hess13) {
   using namespace mpcbk;

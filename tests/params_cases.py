@@ -23,7 +23,7 @@ def mix(names, B, cfg_of):
 
 
 def rows(cfgs, which):
-    """The per-instance config list of a mixed batch (what BatchSolver.params and emu_params.solve take)."""
+    """The per-instance config list of a mixed batch (what BatchSolver.params and emu.solve take)."""
     return [cfgs[k] for k in which]
 
 

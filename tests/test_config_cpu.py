@@ -1,5 +1,5 @@
 """Non-default problem data and solver options without a GPU: every case of tests/config_cases.py through the kernel source stepped
-on the CPU (tests/emu, tests/emu_track for the tracking case) against the oracle, and through the independent certificate of
+on the CPU (tests/emu) against the oracle, and through the independent certificate of
 oracle/kkt_check.py built from the config alone (KinNlp.from_config / DynNlp.from_config).  The device tier of the same table is
 tests/test_config_gpu.py."""
 import numpy as np
@@ -8,7 +8,6 @@ import pytest
 from oracle import oracle, kkt_check
 from tests import config_cases as cc
 from tests.emu import emu
-from tests.emu_track import emu_track
 from mpc_motion_planning_amd import scenes, _abi
 
 
@@ -123,7 +122,7 @@ def test_oracle_solves_enough_of_every_gpu_batch():
 
 def _step_kernel_source(case, cfg, x0, xs, obs, xr):
     if case.track:
-        return emu_track.solve(cfg, x0, xs, xr, obs)
+        return emu.solve(cfg, x0, xs, obs, x_ref=xr)
     return emu.solve(cfg, x0, xs, obs)
 
 

@@ -1,4 +1,4 @@
-"""Per-instance problem data without a GPU: the PARAMS instantiations of the kernel source stepped on the CPU (tests/emu_params) over
+"""Per-instance problem data without a GPU: the PARAMS instantiations of the kernel source stepped on the CPU (tests/emu) over
 the mixed batches of tests/params_cases.py against the oracle and against tests/emu run under each instance's own config, the
 host-side validation of a parameter set, solver.vary, and the machine code of the ten mpcb_param_* kernels.  The device tier is
 tests/test_params_gpu.py."""
@@ -13,7 +13,6 @@ import pytest
 from oracle import oracle
 from tests import config_cases as cc, params_cases as pc
 from tests.emu import emu
-from tests.emu_params import emu_params
 from mpc_motion_planning_amd import scenes, _abi, _lib
 from mpc_motion_planning_amd.solver import BatchSolver, default_config, vary
 
@@ -48,7 +47,7 @@ def test_stepped_mixed_batch_against_oracle_and_per_instance_emu(names):
     oracle); against tests/emu run per instance under that instance's config every output is bit-equal: same source, same arithmetic."""
     K = len(names)
     cases, cfgs, which, x0, xs, obs = pc.mix(names, K, _ocfg)
-    e = emu_params.solve(cfgs[0], pc.rows(cfgs, which), x0, xs, obs)
+    e = emu.solve(cfgs[0], x0, xs, obs, cfgs=pc.rows(cfgs, which))
     r = pc.per_config(lambda c, a, b, o: oracle.solve(c, a, b, o), cfgs, which, x0, xs, obs)
     one = pc.per_config(lambda c, a, b, o: emu.solve(c, a, b, o), cfgs, which, x0, xs, obs)
     dz = np.abs(e["z"] - r["z"]).max(axis=1)
@@ -80,7 +79,7 @@ def test_uniform_rows_equal_the_plain_stepped_source(second_start):
     cfg, x0, xs, obs = _restoration_batch()
     cfg.second_start = second_start
     plain = emu.solve(cfg, x0, xs, obs)
-    e = emu_params.solve(cfg, [cfg] * len(x0), x0, xs, obs)
+    e = emu.solve(cfg, x0, xs, obs, cfgs=[cfg] * len(x0))
     print("uniform rows, second_start %d: status %s iters %s" % (second_start, e["status"].tolist(), e["iters"].tolist()))
     assert pc.bit_equal(e, plain) == []
     off = cfg.copy(); off.restoration = 0; off.second_start = 0

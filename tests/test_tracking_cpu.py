@@ -3,7 +3,7 @@
 The oracle has no tracking cost, so the kernel source is judged by evidence that needs none: with constant rows x_ref[b, i] = c_b the
 tracking NLP IS the oracle's set-point NLP with xs = c_b; with time-varying rows the independent KKT certificate of oracle/kkt_check.py
 (complex-step derivatives) is given the tracking objective through `nlp.xs = x_ref` (KinNlp.f computes X[:-1] - xs).  The kernel
-source is stepped on the CPU by tests/emu_track.  Also here: the C ABI of the new entry points, the drop-in's blend of the window,
+source is stepped on the CPU by tests/emu.  Also here: the C ABI of the new entry points, the drop-in's blend of the window,
 and the machine-code guard of tests/test_kernel_isa.py applied to the mpcb_track_* kernels."""
 import os
 import re
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle, kkt_check
-from tests.emu_track import emu_track
+from tests.emu import emu
 from mpc_motion_planning_amd import scenes, _abi, _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,7 +60,7 @@ def test_constant_rows_equal_the_set_point_solve_of_the_oracle():
     """x_ref[b, i] = c_b is the set-point NLP with xs = c_b: same statuses, iterations and trajectories as the oracle."""
     cfg = product_cfg()
     xr = np.repeat(G["S_xs"][:, None, :], cfg.N, axis=1)
-    e = emu_track.solve(cfg, G["S_x0"], G["S_xs"], xr, G["S_obs"])
+    e = emu.solve(cfg, G["S_x0"], G["S_xs"], G["S_obs"], x_ref=xr)
     assert e["status"][0] == 0 and e["iters"][0] == G["S_iters"][0]
     assert np.abs(e["z"] - G["S_z"]).max() <= 1e-10
     B = 16
@@ -68,7 +68,7 @@ def test_constant_rows_equal_the_set_point_solve_of_the_oracle():
     rng = np.random.default_rng(5)
     c = np.stack([rng.uniform(60, 400, B), rng.uniform(0.0, 4.0, B), np.zeros(B), rng.uniform(10, 30, B)], axis=1)
     xr = np.repeat(c[:, None, :], cfg.N, axis=1)
-    e = emu_track.solve(cfg, x0, xs, xr, obs)                   # the set-point handed to the kernel (xs) is NOT c_b: only x_ref counts
+    e = emu.solve(cfg, x0, xs, obs, x_ref=xr)                   # the set-point handed to the kernel (xs) is NOT c_b: only x_ref counts
     r = oracle.solve(cfg, x0, c, obs)
     assert np.array_equal(e["status"], r["status"]) and np.array_equal(e["iters"], r["iters"])
     assert (r["status"] == 0).sum() >= B // 2
@@ -86,7 +86,7 @@ def test_time_varying_references_pass_the_kkt_certificate(n_obs, integrator):
     obs = G["S_obs"][:1] if n_obs else None
     refs = [lane_change_ref(x0, y_to=0.0), speed_profile_ref(x0)]
     xr = np.stack(refs)
-    e = emu_track.solve(cfg, np.repeat(G["S_x0"], 2, 0), np.repeat(G["S_xs"], 2, 0), xr, None if obs is None else np.repeat(obs, 2, 0))
+    e = emu.solve(cfg, np.repeat(G["S_x0"], 2, 0), np.repeat(G["S_xs"], 2, 0), None if obs is None else np.repeat(obs, 2, 0), x_ref=xr)
     assert (e["status"] == 0).all(), e["status"]
     for b in range(2):
         certify(cfg, x0, xr[b], None if obs is None else obs[0], {k: v[b] for k, v in e.items()}, integrator)
@@ -102,7 +102,7 @@ def test_non_finite_reference_ends_the_instance_with_numeric_status():
     xr = np.repeat(xs[:, None, :], cfg.N, axis=1).copy()
     xr[0, 7, 1] = np.nan
     xr[1, cfg.N - 1, 3] = np.inf
-    e = emu_track.solve(cfg, x0, xs, xr, obs)
+    e = emu.solve(cfg, x0, xs, obs, x_ref=xr)
     assert list(e["status"][:2]) == [_abi.ST_NUMERIC] * 2 and list(e["iters"][:2]) == [0, 0]
     assert e["status"][2] == 0 and np.abs(e["z"][2] - G["S_z"][0]).max() <= 1e-10
 

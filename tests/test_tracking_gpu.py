@@ -1,6 +1,6 @@
 """Per-stage reference tracking on the MI355X (mpcb_solve_ref / mpcb_solve_device_ref / mpcb_closed_loop_ref, the mpcb_track_*
 kernels).  The oracle has no tracking cost: the evidence is the equivalence with the set-point solve (rows equal to xs), the CPU
-stepping of the same kernel source (tests/emu_track), the independent KKT certificate of oracle/kkt_check.py with the tracking
+stepping of the same kernel source (tests/emu), the independent KKT certificate of oracle/kkt_check.py with the tracking
 objective, and a host-driven replay of the tracking closed loop."""
 import numpy as np
 import pytest
@@ -67,7 +67,7 @@ def test_reference_equal_to_set_point_gives_the_set_point_solve(gpu_solver_facto
 
 
 def test_tracking_kernel_equals_its_cpu_stepping(gpu_solver_factory):
-    from tests.emu_track import emu_track
+    from tests.emu import emu
     from oracle import oracle
     B = 16
     x0, xs, obs = scenes.sample_c2(B, seed=111)
@@ -75,7 +75,7 @@ def test_tracking_kernel_equals_its_cpu_stepping(gpu_solver_factory):
     g = gpu_solver_factory(default_config(N=30, n_obs=1)).solve_batch(x0, xs, obs, x_ref=xr)
     c = oracle.default_config(N=30, n_obs=1)
     c.init_rollout = 1; c.mu_init = 10.0; c.second_start = 3; c.start_steer = 0.03
-    e = emu_track.solve(c, x0, xs, xr, obs)
+    e = emu.solve(c, x0, xs, obs, x_ref=xr)
     assert np.array_equal(g["status"], e["status"]) and np.array_equal(g["iters"], e["iters"])
     assert (g["status"] == 0).sum() >= B // 2
     assert np.abs(g["z"] - e["z"]).max() <= 1e-9

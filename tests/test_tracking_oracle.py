@@ -3,13 +3,13 @@
 mpco_solve_ref uses row k of x_ref wherever the main phase of mpco_solve uses xs for stage k < N: the cost (also on the return from the
 restoration phase), the gradient-based objective scaling at the start and the multipliers of the pinned X_0 rows.  It is pinned here by
 the set-point oracle (constant rows) and the independent KKT certificate of oracle/kkt_check.py (time-varying rows); then the TRACK
-instantiations of mpcb_solve_kin, stepped on the CPU by tests/emu_track, are compared with it instance by instance, over the obstacle
+instantiations of mpcb_solve_kin, stepped on the CPU by tests/emu, are compared with it instance by instance, over the obstacle
 counts of the tracking kernels, GEN and RK4 rows, horizons 1..63, a warm start, the four second-start modes and the restoration pass."""
 import numpy as np
 import pytest
 
 from oracle import oracle, kkt_check
-from tests.emu_track import emu_track
+from tests.emu import emu
 from tests.test_tracking_cpu import product_cfg, lane_change_ref, speed_profile_ref, G
 from tests.test_tracking_gpu import random_refs
 from tests.test_gpu_parity import _shift_plan
@@ -180,7 +180,7 @@ def test_kernel_source_matches_the_tracking_oracle(case):
     name, cfg, (x0, xs, obs) = EMU_CASES[case]
     xr = refs(x0, cfg.N, cfg.T, np.random.default_rng(1000 + case))
     r = oracle.solve(cfg, x0, xs, obs, x_ref=xr)
-    e = emu_track.solve(cfg, x0, xs, xr, obs)
+    e = emu.solve(cfg, x0, xs, obs, x_ref=xr)
     same_solve(e, r, name)
     assert (r["status"] == 0).any(), name
 
@@ -195,7 +195,7 @@ def test_kernel_source_matches_the_tracking_oracle_from_a_warm_start():
     z0 = _shift_plan(first["z"], 30, 4)
     x1 = first["z"][:, 64:68].copy()
     r = oracle.solve(cfg, x1, xs, obs, z0=z0, x_ref=path[:, 1:])
-    e = emu_track.solve(cfg, x1, xs, path[:, 1:], obs, z0=z0)
+    e = emu.solve(cfg, x1, xs, obs, z0=z0, x_ref=path[:, 1:])
     same_solve(e, r, "warm start")
     assert (r["status"] == 0).all() and (r["iters"] < first["iters"]).all(), (r["iters"], first["iters"])
 
@@ -210,7 +210,7 @@ def test_kernel_source_matches_the_tracking_oracle_through_restoration():
     sel = [29, 33, 0]
     x0, xs, obs, xr = x0[sel], xs[sel], obs[sel], xr[sel]
     r = oracle.solve(cfg, x0, xs, obs, x_ref=xr)
-    e = emu_track.solve(cfg, x0, xs, xr, obs)
+    e = emu.solve(cfg, x0, xs, obs, x_ref=xr)
     assert r["status"].tolist() == [_abi.ST_INFEASIBLE, _abi.ST_INFEASIBLE, 0], r["status"]
     same_solve(e, r, "restoration")
     cfg.restoration = 0
@@ -229,6 +229,6 @@ def test_kernel_source_non_finite_rows_match_the_oracle():
     xr[0, 12, 2] = np.nan
     xr[1, 0, 3] = np.inf
     r = oracle.solve(cfg, x0, xs, obs, x_ref=xr)
-    e = emu_track.solve(cfg, x0, xs, xr, obs)
+    e = emu.solve(cfg, x0, xs, obs, x_ref=xr)
     assert r["status"][:2].tolist() == [_abi.ST_NUMERIC] * 2 and r["iters"][:2].tolist() == [0, 0]
     same_solve(e, r, "non-finite rows")
