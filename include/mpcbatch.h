@@ -27,6 +27,8 @@
  *     overlap (bench.py's default: one handle, sixteen lanes); distinct handles are independent as well.
  *   - buffers of solves that are in flight at the same time (lanes, or several handles) must be distinct: in particular the
  *     status array, through which the two passes of a solve communicate.
+ *   - a receding horizon runs either whole on the device (mpcb_closed_loop: the library's plant and obstacle motion) or one controller
+ *     step per call with the controller's state resident between calls (mpcb_loop_*: the caller's plant, obstacles and episode ends).
  */
 #ifndef MPCBATCH_H
 #define MPCBATCH_H
@@ -336,6 +338,59 @@ int mpcb_solve_device_params(mpcb_handle* h, int32_t B, const mpcb_params* p,
 int mpcb_closed_loop_params(mpcb_handle* h, int32_t B, int32_t steps, const mpcb_params* p,
                             const double* x0, const double* xs, double* obs_state, int32_t obs_motion, int32_t flags,
                             double* x_hist, double* u_hist, int32_t* status_hist, int32_t* iters_hist);
+
+/* ---- the stepwise loop: controller state on the device, plant outside ----------------------------------------------------------
+ * mpcb_closed_loop runs `steps` iterations against the library's own plant and its own constant-velocity obstacles.  These entries are
+ * ONE step of that controller as a call, for callers whose plant is their own simulator, whose obstacles come from their own
+ * perception at every step, and whose episodes end and restart per instance.  A loop (mpcb_loop_create) owns, on the handle's device:
+ * the warm start w [B, nz] (zero after create and reset: what mpcb_closed_loop starts from), a trajectory buffer for MPCB_LOOP_PREDICT,
+ * status / iters columns for callers that pass none, and per-instance counters of steps and failed steps since the last reset.
+ *   flags            MPCB_CL_HOLD_ON_FAILURE (as in mpcb_closed_loop) | MPCB_LOOP_PREDICT (STATIC obstacle rows given to a step are
+ *                    rolled out at constant velocity over the handle's T or time grid before the solve, as MPCB_OBSMOVE_PREDICTED does;
+ *                    PREDICTED trajectories given to such a loop are used as given)
+ *   p                NULL = the handle's config, or a live parameter set of h with B rows: instance b is solved, and stepped by
+ *                    mpcb_loop_advance_device, under row b.  The set is re-checked at every call, as mpcb_solve_params does.
+ *   mpcb_loop_step   one controller step for every instance b:
+ *                      1. [predict]  2. the solve that mpcb_solve_device / _ref / _params launches, started from w (a start vector is
+ *                      always given: second_start = 3 acts as 2, no turned cold start, as in every step of mpcb_closed_loop); x_ref
+ *                      [B, N, nx] != NULL selects the tracking kernels, xs and x_ref may change from step to step (a caller-supplied
+ *                      path or a set-point schedule is the caller's x_ref / xs per step);
+ *                      3. commit: the executed plan is w when the loop holds on failure and the status is neither MPCB_ST_SOLVED nor
+ *                      MPCB_ST_ACCEPTABLE, else this step's z; u0[b] = the plan's first control, w = the plan shifted one stage; the
+ *                      counters are bumped.  z, obj, status and iters are the solve's own outputs, unmodified.
+ *                    Host pointers; waits for the lanes and runs on the handle's stream, like mpcb_closed_loop.
+ *   mpcb_loop_step_device      the same with device pointers (caller-owned, distinct per loop), asynchronous unless sync != 0.
+ *   mpcb_loop_advance_device   the other half of mpcb_closed_loop's step on caller-owned device arrays: the library's plant
+ *                    d_x0 <- d_x0 + T f(d_x0, d_u0) (T = T_0 of the time grid or cfg.T; RK4 when cfg.integrator says so; constants of
+ *                    row b when the loop has a set) and one constant-velocity step of every obstacle of d_obs [B, n_obs, 6] (flags =
+ *                    MPCB_CL_ADVANCE_FIRST_ONLY: of obstacle 0 alone; d_obs = NULL: of none).  (mpcb_loop_step_device, then
+ *                    mpcb_loop_advance_device) repeated reproduces mpcb_closed_loop bit for bit.
+ *   lanes            the two _device entries of a loop run on lane (loop id mod k), id = creation order on the handle, k = the current
+ *                    mpcb_set_inflight: the steps of one loop are ordered, steps of loops on different lanes overlap.  Results do not
+ *                    depend on k.  Every other loop entry waits for the lanes first.
+ *   mpcb_loop_reset  warm start and counters back to zero for the instances with mask[b] != 0 (host [B]; NULL = every instance).
+ *   mpcb_loop_get_start / _set_start   download / replace w (host [B, nz]): a loop seeded from another loop's start continues it.
+ *   mpcb_loop_counters   steps and failed steps (status neither SOLVED nor ACCEPTABLE) per instance since the last reset (host [B] each,
+ *                    either may be NULL).
+ *   mpcb_loop_destroy    waits for the lanes and the stream, then frees the loop; loops still alive at mpcb_destroy are freed there.
+ * What the solve entries refuse is refused here with their code and text (tracking on MPCB_MODEL_DYN, x_ref together with a set, ...);
+ * a device group (mpcb_set_devices) is MPCB_E_UNSUPPORTED.  A NULL handle or loop, a loop of another handle, B < 1, unknown flags, a
+ * set of another B or one the handle no longer matches, a required pointer that is NULL: MPCB_E_INVALID. */
+typedef struct mpcb_loop mpcb_loop;
+#define MPCB_LOOP_PREDICT 4   /* or-ed with MPCB_CL_HOLD_ON_FAILURE (1) */
+int mpcb_loop_create(mpcb_handle* h, int32_t B, int32_t flags, const mpcb_params* p, mpcb_loop** out);
+int mpcb_loop_destroy(mpcb_handle* h, mpcb_loop* L);
+int mpcb_loop_reset(mpcb_handle* h, mpcb_loop* L, const int32_t* mask);
+int mpcb_loop_get_start(mpcb_handle* h, mpcb_loop* L, double* z0);
+int mpcb_loop_set_start(mpcb_handle* h, mpcb_loop* L, const double* z0);
+int mpcb_loop_counters(mpcb_handle* h, mpcb_loop* L, int32_t* steps, int32_t* failures);
+int mpcb_loop_step(mpcb_handle* h, mpcb_loop* L,
+                   const double* x0, const double* xs, const double* x_ref, const double* obs, int32_t obs_kind,
+                   double* u0, int32_t* status, int32_t* iters, double* z, double* obj);
+int mpcb_loop_step_device(mpcb_handle* h, mpcb_loop* L,
+                          const double* d_x0, const double* d_xs, const double* d_x_ref, const double* d_obs, int32_t obs_kind,
+                          double* d_u0, int32_t* d_status, int32_t* d_iters, double* d_z, double* d_obj, int32_t sync);
+int mpcb_loop_advance_device(mpcb_handle* h, mpcb_loop* L, double* d_x0, const double* d_u0, double* d_obs, int32_t flags, int32_t sync);
 
 /* ---- scene generation on the device -----------------------------------------------------------------------
  * Counter-based random scenes (Philox4x32-10 keyed by `seed`, counter = global scene index): scene i is the same whichever GPU,

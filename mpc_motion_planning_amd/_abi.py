@@ -18,6 +18,7 @@ OBSIN_STATIC, OBSIN_PREDICTED = 0, 1
 MU_MONOTONE = 0
 INT_EULER, INT_RK4 = 0, 1
 CL_HOLD_ON_FAILURE, CL_ADVANCE_FIRST_ONLY = 1, 2
+LOOP_PREDICT = 4
 OBSMOVE_STATIC, OBSMOVE_PREDICTED, OBSMOVE_CURRENT = 0, 1, 2
 NX_MAX, NU, NOBS_MAX, N_MAX = 6, 2, 8, 63
 UNIQUE_ID_BYTES = 128

@@ -43,6 +43,16 @@ SIGNATURES = {
     "mpcb_solve_device_params": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "mpcb_closed_loop_params": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, _PD, _PD, _PD, C.c_int32, C.c_int32, _PD, _PD, _PI, _PI]),
+    "mpcb_loop_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mpcb_loop_destroy": (C.c_int, [_H, C.c_void_p]),
+    "mpcb_loop_reset": (C.c_int, [_H, C.c_void_p, _PI]),
+    "mpcb_loop_get_start": (C.c_int, [_H, C.c_void_p, _PD]),
+    "mpcb_loop_set_start": (C.c_int, [_H, C.c_void_p, _PD]),
+    "mpcb_loop_counters": (C.c_int, [_H, C.c_void_p, _PI, _PI]),
+    "mpcb_loop_step": (C.c_int, [_H, C.c_void_p, _PD, _PD, _PD, _PD, C.c_int32, _PD, _PI, _PI, _PD, _PD]),
+    "mpcb_loop_step_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "mpcb_loop_advance_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "mpcb_sample_scenes": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mpcb_closed_loop_sampled": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PI, _PI]),
     "mpcb_predict_obstacles": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_double, _PD, _PD]),

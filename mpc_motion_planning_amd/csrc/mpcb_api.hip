@@ -300,6 +300,112 @@ __global__ __launch_bounds__(128) void mpcb_advance_params(const mpcb_config* __
   }
 }
 
+// ---- the stepwise loop (mpcb_loop_*): mpcb_advance cut at the seam between controller and plant ---------------------------------------
+// mpcb_loop_commit is the controller's half: which plan is executed (hold-and-shift), its first control to u0, the plan shifted one stage
+// into the warm start w, the counters.  mpcb_loop_plant is the plant's half: x0 <- x0 + T f(x0, u0) and the obstacle move.  Both repeat
+// mpcb_advance's expressions in its order, so that (commit, plant) after a solve leaves exactly what mpcb_advance leaves.
+// one thread per instance
+template <int NX>
+__global__ __launch_bounds__(128) void mpcb_loop_commit(int B, int N, int nz, const double* __restrict__ z, double* __restrict__ w0,
+                                                        double* __restrict__ u0, const int32_t* __restrict__ status, int hold,
+                                                        int32_t* __restrict__ n_steps, int32_t* __restrict__ n_failed) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double* w = w0 + (size_t)b * nz;
+  const int st_b = status[b];
+  const bool failed = st_b != MPCB_ST_SOLVED && st_b != MPCB_ST_ACCEPTABLE;
+  const bool keep = hold && failed;
+  const double* zb = keep ? w : z + (size_t)b * nz;
+  u0[(size_t)b * 2] = zb[0]; u0[(size_t)b * 2 + 1] = zb[1];
+  // u <- [u[1:]; u[-1]],  x_f <- [x_f[1:]; x_f[-1]]   (in place when zb == w: ascending order reads ahead of the writes)
+  for (int i = 0; i < N; ++i) { int s = (i + 1 < N) ? i + 1 : N - 1; const double a0 = zb[2 * s], a1 = zb[2 * s + 1]; w[2 * i] = a0; w[2 * i + 1] = a1; }
+  for (int i = 0; i <= N; ++i) {
+    int s = (i + 1 <= N) ? i + 1 : N;
+    double t[NX];
+#pragma unroll
+    for (int q = 0; q < NX; ++q) t[q] = zb[2 * N + NX * s + q];
+#pragma unroll
+    for (int q = 0; q < NX; ++q) w[2 * N + NX * i + q] = t[q];
+  }
+  n_steps[b] += 1;
+  if (failed) n_failed[b] += 1;
+}
+
+// model_rhs with the model fixed at compile time by NX (4: kinematic, 6: dynamic): the expressions of model_rhs, copied, in its order.
+// A copy and not a call: with the model a run-time branch the compiler indexes xdot[] dynamically and parks it in scratch (mpcb_advance
+// does), and a further caller of model_rhs moves the instruction text of the existing kernels.
+template <int NX>
+__device__ __forceinline__ void mpcb_loop_rhs(const mpcb_config& c, const double* x, const double* u, double* xdot) {
+#pragma clang fp contract(off)
+  if constexpr (NX == 4) {
+    xdot[0] = x[3] * cos(x[2]);
+    xdot[1] = x[3] * sin(x[2]);
+    xdot[2] = x[3] * tan(u[0]) / c.veh_l;
+    xdot[3] = u[1];
+  } else {
+    const double phi = x[2], vx = x[3], vy = x[4], r = x[5], df = u[0], ax = u[1];
+    const double af = df - (vy + c.veh_lf * r) / vx, ar = -(vy - c.veh_lr * r) / vx;
+    const double Cf = c.Fymax_f * 2 * c.aopt_f / (c.aopt_f * c.aopt_f + af * af);
+    const double Cr = c.Fymax_r * 2 * c.aopt_r / (c.aopt_r * c.aopt_r + ar * ar);
+    const double Fcf = -Cf * af, Fcr = -Cr * ar;
+    xdot[0] = vx * cos(phi) - vy * sin(phi);
+    xdot[1] = vx * sin(phi) + vy * cos(phi);
+    xdot[2] = r;
+    xdot[3] = ax + r * vy;
+    xdot[4] = -r * vx + 2.0 / c.veh_m * (Fcf * cos(df) + Fcr);
+    xdot[5] = 2.0 / c.veh_Iz * (c.veh_lf * Fcf - c.veh_lr * Fcr);
+  }
+}
+
+// cfgs: [B] per-instance configs (the loop was created with a parameter set: constants of row b, as in mpcb_advance_params), or NULL
+//   move_obs: 0 none, 1 every obstacle one constant-velocity step, 2 only the first one
+template <int NX>
+__global__ __launch_bounds__(128) void mpcb_loop_plant(const mpcb_config c0, const mpcb_config* __restrict__ cfgs, int B, double* __restrict__ x0,
+                                                       const double* __restrict__ u0, double* __restrict__ obs, int move_obs, double T) {
+#pragma clang fp contract(off)   // as mpcb_advance: every product and sum rounded on its own
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const mpcb_config& c = cfgs ? cfgs[b] : c0;
+  const int n_obs = c0.n_obs;             // structural: the same in every row
+  double* xb = x0 + (size_t)b * NX;
+  const double u[2] = {u0[(size_t)b * 2], u0[(size_t)b * 2 + 1]};
+  double x[NX], f[NX];
+#pragma unroll
+  for (int q = 0; q < NX; ++q) x[q] = xb[q];
+  mpcb_loop_rhs<NX>(c, x, u, f);
+  if (c0.integrator == MPCB_INT_RK4) {
+    double k2[NX], k3[NX], k4[NX], xt[NX];
+#pragma unroll
+    for (int q = 0; q < NX; ++q) xt[q] = x[q] + 0.5 * T * f[q];
+    mpcb_loop_rhs<NX>(c, xt, u, k2);
+#pragma unroll
+    for (int q = 0; q < NX; ++q) xt[q] = x[q] + 0.5 * T * k2[q];
+    mpcb_loop_rhs<NX>(c, xt, u, k3);
+#pragma unroll
+    for (int q = 0; q < NX; ++q) xt[q] = x[q] + T * k3[q];
+    mpcb_loop_rhs<NX>(c, xt, u, k4);
+#pragma unroll
+    for (int q = 0; q < NX; ++q) f[q] = (f[q] + 2.0 * k2[q] + 2.0 * k3[q] + k4[q]) / 6.0;
+  }
+#pragma unroll
+  for (int q = 0; q < NX; ++q) xb[q] = x[q] + T * f[q];
+  const int nmove = move_obs == 1 ? n_obs : move_obs == 2 ? (n_obs < 1 ? n_obs : 1) : 0;
+  for (int j = 0; j < nmove; ++j) {
+    double* o = obs + ((size_t)b * n_obs + j) * 6;
+    o[0] += o[3] * cos(o[2]) * T; o[1] += o[3] * sin(o[2]) * T;
+  }
+}
+
+// mpcb_loop_reset with a mask: the warm start and the counters of the masked instances back to zero
+__global__ __launch_bounds__(128) void mpcb_loop_clear(int B, int nz, const int32_t* __restrict__ mask, double* __restrict__ w0,
+                                                       int32_t* __restrict__ n_steps, int32_t* __restrict__ n_failed) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B || !mask[b]) return;
+  double* w = w0 + (size_t)b * nz;
+  for (int i = 0; i < nz; ++i) w[i] = 0.0;
+  n_steps[b] = 0; n_failed[b] = 0;
+}
+
 // constant-velocity prediction of every obstacle over the horizon: [B, n_obs, 6] -> [B, n_obs, N+1, 6]
 __global__ void mpcb_predict_obs(int total, int N, double T, const double* __restrict__ tgrid, const double* __restrict__ obs, double* __restrict__ traj) {
 #pragma clang fp contract(off)   // next_x = x + v*cos(theta)*dt, two roundings per step as in Obs_prediction.py:27-28
@@ -457,6 +563,20 @@ struct mpcb_params {
   mpcb_config* d_cfgs = nullptr;     // [B] on the owner's device
 };
 
+// a stepwise control loop (mpcb_loop_create): the controller's state of B instances, resident on the owner's device between steps
+struct mpcb_loop {
+  mpcb_handle* owner = nullptr;
+  int32_t B = 0, flags = 0;
+  int id = 0;                        // creation order on the handle: asynchronous steps run on lane id mod K
+  const mpcb_params* params = nullptr;   // the set the loop was created with (checked against the handle's live sets before every use)
+  double* d_w = nullptr;             // [B, nz] warm start: the executed plan shifted one stage; zero after create / reset
+  double* d_z = nullptr;             // [B, nz] the solve's iterate when the caller passes no z
+  double* d_traj = nullptr;          // [B, n_obs, N+1, 6] MPCB_LOOP_PREDICT roll-out
+  int32_t* d_st = nullptr;           // [B] status / iters columns when the caller passes none
+  int32_t* d_it = nullptr;
+  int32_t* d_cnt = nullptr;          // [2, B] steps and failed steps since the last reset
+};
+
 struct mpcb_handle {
   mpcb_config cfg;
   int device = 0;
@@ -492,6 +612,8 @@ struct mpcb_handle {
   size_t gathered_rows = 0;                            // (b): rows per shard block of the last gather, B of that solve
   int64_t gathered_B = 0;
   std::vector<mpcb_params*> params;                    // live parameter sets of this handle (mpcb_destroy frees what the caller left)
+  std::vector<mpcb_loop*> loops;                       // live stepwise loops of this handle (freed at mpcb_destroy likewise)
+  int loops_created = 0;                               // the next loop's id
 };
 
 namespace {
@@ -871,6 +993,92 @@ int check_params_use(mpcb_handle* h, const mpcb_params* p, int32_t B) {
   return MPCB_OK;
 }
 
+// ---- stepwise loops ----------------------------------------------------------------------------------------------------------------
+void free_loop_buffers(mpcb_loop* L) {
+  if (L->d_w) (void)hipFree(L->d_w);
+  if (L->d_z) (void)hipFree(L->d_z);
+  if (L->d_traj) (void)hipFree(L->d_traj);
+  if (L->d_st) (void)hipFree(L->d_st);
+  if (L->d_it) (void)hipFree(L->d_it);
+  if (L->d_cnt) (void)hipFree(L->d_cnt);
+  L->d_w = L->d_z = L->d_traj = nullptr; L->d_st = L->d_it = L->d_cnt = nullptr;
+}
+
+// may h use the loop L?  L is looked up among h's live loops before it is read, so a destroyed loop or one of another handle is an error code.
+// The loop's parameter set goes through the checks of mpcb_solve_params again (alive, same B, the handle still matches it structurally).
+int check_loop_use(mpcb_handle* h, const mpcb_loop* L) {
+  if (!h) return fail(h, MPCB_E_INVALID, "the handle is NULL");
+  if (!L) return fail(h, MPCB_E_INVALID, "the loop is NULL");
+  bool mine = false;
+  for (auto* q : h->loops) mine = mine || q == L;
+  if (!mine) return fail(h, MPCB_E_INVALID, "the loop does not belong to this handle (or was destroyed)");
+  if (!h->peers.empty()) return fail(h, MPCB_E_UNSUPPORTED, "stepwise loops do not run on a device group (mpcb_set_devices)");
+  if (L->params) return check_params_use(h, L->params, L->B);
+  return MPCB_OK;
+}
+
+// the lane an asynchronous call of the loop runs on: loop id mod K, K the current mpcb_set_inflight
+int loop_lane(mpcb_handle* h, const mpcb_loop* L) {
+  const int K = h->lanes.empty() ? 1 : (int)h->lanes.size();
+  return L->id % K;
+}
+
+// work queued so far on the handle's stream (uploads, scene sampling, a reset) happens before what a lane is given next
+int lane_follows_handle(mpcb_handle* h, int lane) {
+  if (h->lanes.empty()) { int rc = ensure_lanes(h, 1); if (rc != MPCB_OK) return rc; }
+  if (lane > 0) {
+    HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->lanes[lane].stream, h->ev_fork, 0));
+  }
+  return MPCB_OK;
+}
+
+int lane_done(mpcb_handle* h, int lane) {
+  if (lane > 0) { auto& Ln = h->lanes[lane]; HIP_TRY(h, hipEventRecord(Ln.done, Ln.stream)); Ln.busy = true; }
+  return MPCB_OK;
+}
+
+// (named before closed_loop_impl names mpcb_advance: kernels are emitted in the order of their first use, and mpcb_advance<4> stays the
+// last function of the code object, where the resource table of tools/kernel_resources.py counts no trailing padding for it)
+void launch_loop_plant(int nx, hipStream_t s, const mpcb_config& cfg, const mpcb_config* d_cfgs, int B, double* x0, const double* u0, double* obs,
+                       int move_obs, double T) {
+  if (nx == 6)
+    hipLaunchKernelGGL(mpcb_loop_plant<6>, dim3((B + 127) / 128), dim3(128), 0, s, cfg, d_cfgs, B, x0, u0, obs, move_obs, T);
+  else
+    hipLaunchKernelGGL(mpcb_loop_plant<4>, dim3((B + 127) / 128), dim3(128), 0, s, cfg, d_cfgs, B, x0, u0, obs, move_obs, T);
+}
+
+// One controller step with everything on the device, queued on lane `lane`: [predict ->] solve from the loop's warm start -> commit.
+// Every refusal comes before the first launch, so a refused step leaves the loop as it was.
+int loop_step_on_device(mpcb_handle* h, mpcb_loop* L, const double* x0, const double* xs, const double* x_ref, const double* obs, int32_t obs_kind,
+                        double* u0, int32_t* status, int32_t* iters, double* z, double* obj, int lane) {
+  if (!x0 || !xs || !u0) return fail(h, MPCB_E_INVALID, "a required pointer is NULL (x0, xs and u0 are required)");
+  const int B = L->B, N = h->cfg.N, no = h->cfg.n_obs, nz = h->nz;
+  if (x_ref) { int rc = check_track(h); if (rc != MPCB_OK) return rc; }
+  SolveArgs sv = solve_args(B, x0, xs, obs, obs_kind, L->d_w, z ? z : L->d_z, obj, status ? status : L->d_st, iters ? iters : L->d_it,
+                            nullptr, nullptr, nullptr);
+  sv.xref = x_ref; sv.cfgs = L->params ? L->params->d_cfgs : nullptr;
+  { int rc = check_solve_args(h, sv, true); if (rc != MPCB_OK) return rc; }
+  { mpcbd::Variant v; int rc = variant_or_fail(h, h->cfg, sv.xref != nullptr, sv.cfgs != nullptr, &v); if (rc != MPCB_OK) return rc; }
+  HIP_TRY(h, hipSetDevice(h->device));
+  { int rc = lane_follows_handle(h, lane); if (rc != MPCB_OK) return rc; }
+  const hipStream_t s = h->lanes[lane].stream;
+  if ((L->flags & MPCB_LOOP_PREDICT) && obs_kind == MPCB_OBSIN_STATIC && no > 0) {
+    const int total = B * no;
+    hipLaunchKernelGGL(mpcb_predict_obs, dim3((total + 255) / 256), dim3(256), 0, s, total, N, h->cfg.T, h->d_tgrid, obs, L->d_traj);
+    HIP_TRY(h, hipGetLastError());
+    sv.obs = L->d_traj; sv.obs_kind = MPCB_OBSIN_PREDICTED;
+  }
+  { int rc = solve_on_device(h, sv, lane); if (rc != MPCB_OK) return rc; }
+  const int hold = (L->flags & MPCB_CL_HOLD_ON_FAILURE) ? 1 : 0;
+  if (h->nx == 6)
+    hipLaunchKernelGGL(mpcb_loop_commit<6>, dim3((B + 127) / 128), dim3(128), 0, s, B, N, nz, sv.z, L->d_w, u0, sv.status, hold, L->d_cnt, L->d_cnt + B);
+  else
+    hipLaunchKernelGGL(mpcb_loop_commit<4>, dim3((B + 127) / 128), dim3(128), 0, s, B, N, nz, sv.z, L->d_w, u0, sv.status, hold, L->d_cnt, L->d_cnt + B);
+  HIP_TRY(h, hipGetLastError());
+  return lane_done(h, lane);            // the lane's `done` now marks the end of the commit, not of the solve
+}
+
 }  // namespace
 
 extern "C" {
@@ -977,6 +1185,8 @@ int mpcb_destroy(mpcb_handle* h) {
   }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   for (auto& m : h->marks) for (auto e : m) (void)hipEventDestroy(e);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (auto* L : h->loops) { free_loop_buffers(L); delete L; }       // the lanes have been waited for above
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return MPCB_OK;
@@ -1474,6 +1684,164 @@ int mpcb_closed_loop_params(mpcb_handle* h, int32_t B, int32_t steps, const mpcb
   { int rc = check_params_use(h, p, B); if (rc != MPCB_OK) return rc; }
   return closed_loop_impl(h, B, steps, x0, xs, obs_state, obs_motion, flags, x_hist, u_hist, status_hist, iters_hist, 0, 0, 0, nullptr, nullptr,
                           false, 0.0, p->d_cfgs);
+}
+
+// ---- the stepwise loop: controller state on the device, plant outside -------------------------------------------------------------
+int mpcb_loop_create(mpcb_handle* h, int32_t B, int32_t flags, const mpcb_params* p, mpcb_loop** out) {
+  if (!h) return fail(h, MPCB_E_INVALID, "the handle is NULL");
+  if (!out) return fail(h, MPCB_E_INVALID, "out is NULL");
+  *out = nullptr;
+  if (B < 1) return fail(h, MPCB_E_INVALID, "B = %d, a loop holds at least one instance", B);
+  if (flags & ~(MPCB_CL_HOLD_ON_FAILURE | MPCB_LOOP_PREDICT)) return fail(h, MPCB_E_INVALID, "unknown flags 0x%x", flags);
+  if (!h->peers.empty()) return fail(h, MPCB_E_UNSUPPORTED, "stepwise loops do not run on a device group (mpcb_set_devices)");
+  if (p) { int rc = check_params_use(h, p, B); if (rc != MPCB_OK) return rc; }
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t nz = h->nz, n_traj = (flags & MPCB_LOOP_PREDICT) ? (size_t)B * h->cfg.n_obs * (h->cfg.N + 1) * 6 : 0;
+  mpcb_loop* L = new mpcb_loop();
+  L->owner = h; L->B = B; L->flags = flags; L->params = p;
+  hipError_t e = hipMalloc(&L->d_w, (size_t)B * nz * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&L->d_z, (size_t)B * nz * sizeof(double));
+  if (e == hipSuccess && n_traj) e = hipMalloc(&L->d_traj, n_traj * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&L->d_st, (size_t)B * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc(&L->d_it, (size_t)B * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc(&L->d_cnt, (size_t)2 * B * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemsetAsync(L->d_w, 0, (size_t)B * nz * sizeof(double), h->stream);   // u0 = 0, next_states = 0: what closed_loop_impl starts from
+  if (e == hipSuccess) e = hipMemsetAsync(L->d_cnt, 0, (size_t)2 * B * sizeof(int32_t), h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    free_loop_buffers(L);
+    delete L;
+    return fail(h, MPCB_E_DEVICE, "allocating a loop of %d instances: %s", B, hipGetErrorString(e));
+  }
+  L->id = h->loops_created++;
+  h->loops.push_back(L);
+  *out = L;
+  return MPCB_OK;
+}
+
+int mpcb_loop_destroy(mpcb_handle* h, mpcb_loop* L) {
+  if (!h) return fail(h, MPCB_E_INVALID, "the handle is NULL");
+  if (!L) return MPCB_OK;
+  size_t at = h->loops.size();
+  for (size_t i = 0; i < h->loops.size(); ++i) if (h->loops[i] == L) at = i;
+  if (at == h->loops.size()) return fail(h, MPCB_E_INVALID, "the loop does not belong to this handle (or was destroyed)");
+  { int rc = mpcb_sync(h); if (rc != MPCB_OK) return rc; }       // lanes joined, nothing in flight still uses the loop's buffers
+  h->loops.erase(h->loops.begin() + at);
+  free_loop_buffers(L);
+  delete L;
+  return MPCB_OK;
+}
+
+int mpcb_loop_reset(mpcb_handle* h, mpcb_loop* L, const int32_t* mask) {
+  { int rc = check_loop_use(h, L); if (rc != MPCB_OK) return rc; }
+  HIP_TRY(h, hipSetDevice(h->device));
+  { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
+  const int B = L->B, nz = h->nz;
+  hipStream_t s = h->stream;
+  if (!mask) {
+    HIP_TRY(h, hipMemsetAsync(L->d_w, 0, (size_t)B * nz * sizeof(double), s));
+    HIP_TRY(h, hipMemsetAsync(L->d_cnt, 0, (size_t)2 * B * sizeof(int32_t), s));
+  } else {
+    { int rc = ensure_scratch(h, (size_t)B * sizeof(int32_t) + 256); if (rc != MPCB_OK) return rc; }
+    int32_t* d_mask = (int32_t*)h->d_buf;
+    HIP_TRY(h, hipMemcpyAsync(d_mask, mask, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(mpcb_loop_clear, dim3((B + 127) / 128), dim3(128), 0, s, B, nz, d_mask, L->d_w, L->d_cnt, L->d_cnt + B);
+    HIP_TRY(h, hipGetLastError());
+  }
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return MPCB_OK;
+}
+
+int mpcb_loop_get_start(mpcb_handle* h, mpcb_loop* L, double* z0) {
+  { int rc = check_loop_use(h, L); if (rc != MPCB_OK) return rc; }
+  if (!z0) return fail(h, MPCB_E_INVALID, "z0 is NULL");
+  HIP_TRY(h, hipSetDevice(h->device));
+  { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
+  HIP_TRY(h, hipMemcpyAsync(z0, L->d_w, (size_t)L->B * h->nz * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MPCB_OK;
+}
+
+int mpcb_loop_set_start(mpcb_handle* h, mpcb_loop* L, const double* z0) {
+  { int rc = check_loop_use(h, L); if (rc != MPCB_OK) return rc; }
+  if (!z0) return fail(h, MPCB_E_INVALID, "z0 is NULL");
+  HIP_TRY(h, hipSetDevice(h->device));
+  { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
+  HIP_TRY(h, hipMemcpyAsync(L->d_w, z0, (size_t)L->B * h->nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MPCB_OK;
+}
+
+int mpcb_loop_counters(mpcb_handle* h, mpcb_loop* L, int32_t* steps, int32_t* failures) {
+  { int rc = check_loop_use(h, L); if (rc != MPCB_OK) return rc; }
+  HIP_TRY(h, hipSetDevice(h->device));
+  { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
+  if (steps) HIP_TRY(h, hipMemcpyAsync(steps, L->d_cnt, (size_t)L->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (failures) HIP_TRY(h, hipMemcpyAsync(failures, L->d_cnt + L->B, (size_t)L->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return MPCB_OK;
+}
+
+int mpcb_loop_step_device(mpcb_handle* h, mpcb_loop* L, const double* d_x0, const double* d_xs, const double* d_x_ref, const double* d_obs,
+                          int32_t obs_kind, double* d_u0, int32_t* d_status, int32_t* d_iters, double* d_z, double* d_obj, int32_t sync) {
+  { int rc = check_loop_use(h, L); if (rc != MPCB_OK) return rc; }
+  int rc = loop_step_on_device(h, L, d_x0, d_xs, d_x_ref, d_obs, obs_kind, d_u0, d_status, d_iters, d_z, d_obj, loop_lane(h, L));
+  if (rc != MPCB_OK) return rc;
+  return sync ? mpcb_sync(h) : MPCB_OK;
+}
+
+int mpcb_loop_step(mpcb_handle* h, mpcb_loop* L, const double* x0, const double* xs, const double* x_ref, const double* obs, int32_t obs_kind,
+                   double* u0, int32_t* status, int32_t* iters, double* z, double* obj) {
+  { int rc = check_loop_use(h, L); if (rc != MPCB_OK) return rc; }
+  if (!x0 || !xs || !u0) return fail(h, MPCB_E_INVALID, "a required pointer is NULL (x0, xs and u0 are required)");
+  if (h->cfg.n_obs > 0 && !obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
+  if (obs_kind != MPCB_OBSIN_STATIC && obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", obs_kind);
+  HIP_TRY(h, hipSetDevice(h->device));
+  { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
+  const int nx = h->nx, N = h->cfg.N;
+  const size_t B = (size_t)L->B, nz = h->nz;
+  const size_t n_obs_d = B * h->cfg.n_obs * 6 * (obs_kind == MPCB_OBSIN_PREDICTED ? N + 1 : 1);
+  double *d_x0, *d_xs, *d_obs, *d_xr, *d_u0, *d_obj;
+  auto carve = [&](Carve& cv) {
+    d_x0 = cv.take<double>(B * nx);
+    d_xs = cv.take<double>(B * nx);
+    d_obs = n_obs_d ? cv.take<double>(n_obs_d) : nullptr;
+    d_xr = x_ref ? cv.take<double>(B * N * 4) : nullptr;
+    d_u0 = cv.take<double>(B * 2);
+    d_obj = obj ? cv.take<double>(B) : nullptr;
+  };
+  { Carve dry{nullptr}; carve(dry); int rc = ensure_scratch(h, dry.bytes()); if (rc != MPCB_OK) return rc; }
+  { Carve cv{(char*)h->d_buf}; carve(cv); }
+  hipStream_t s = h->stream;
+  HIP_TRY(h, hipMemcpyAsync(d_x0, x0, B * nx * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(d_xs, xs, B * nx * 8, hipMemcpyHostToDevice, s));
+  if (d_obs) HIP_TRY(h, hipMemcpyAsync(d_obs, obs, n_obs_d * 8, hipMemcpyHostToDevice, s));
+  if (d_xr) HIP_TRY(h, hipMemcpyAsync(d_xr, x_ref, B * N * 4 * 8, hipMemcpyHostToDevice, s));
+  { int rc = loop_step_on_device(h, L, d_x0, d_xs, d_xr, d_obs, obs_kind, d_u0, nullptr, nullptr, nullptr, d_obj, 0); if (rc != MPCB_OK) return rc; }
+  HIP_TRY(h, hipMemcpyAsync(u0, d_u0, B * 2 * 8, hipMemcpyDeviceToHost, s));
+  if (status) HIP_TRY(h, hipMemcpyAsync(status, L->d_st, B * 4, hipMemcpyDeviceToHost, s));
+  if (iters) HIP_TRY(h, hipMemcpyAsync(iters, L->d_it, B * 4, hipMemcpyDeviceToHost, s));
+  if (z) HIP_TRY(h, hipMemcpyAsync(z, L->d_z, B * nz * 8, hipMemcpyDeviceToHost, s));
+  if (obj) HIP_TRY(h, hipMemcpyAsync(obj, d_obj, B * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return MPCB_OK;
+}
+
+int mpcb_loop_advance_device(mpcb_handle* h, mpcb_loop* L, double* d_x0, const double* d_u0, double* d_obs, int32_t flags, int32_t sync) {
+  { int rc = check_loop_use(h, L); if (rc != MPCB_OK) return rc; }
+  if (!d_x0 || !d_u0) return fail(h, MPCB_E_INVALID, "a required pointer is NULL (d_x0 and d_u0 are required)");
+  if (flags & ~MPCB_CL_ADVANCE_FIRST_ONLY) return fail(h, MPCB_E_INVALID, "unknown flags 0x%x (0 or MPCB_CL_ADVANCE_FIRST_ONLY)", flags);
+  HIP_TRY(h, hipSetDevice(h->device));
+  const int lane = loop_lane(h, L), B = L->B;
+  { int rc = lane_follows_handle(h, lane); if (rc != MPCB_OK) return rc; }
+  const hipStream_t s = h->lanes[lane].stream;
+  const int move = (!d_obs || h->cfg.n_obs == 0) ? 0 : (flags & MPCB_CL_ADVANCE_FIRST_ONLY) ? 2 : 1;
+  const double Tstep = h->d_tgrid ? h->T0 : h->cfg.T;
+  const mpcb_config* d_cfgs = L->params ? L->params->d_cfgs : nullptr;
+  launch_loop_plant(h->nx, s, h->cfg, d_cfgs, B, d_x0, d_u0, d_obs, move, Tstep);
+  HIP_TRY(h, hipGetLastError());
+  { int rc = lane_done(h, lane); if (rc != MPCB_OK) return rc; }
+  return sync ? mpcb_sync(h) : MPCB_OK;
 }
 
 int mpcb_closed_loop_sampled(mpcb_handle* h, int32_t kind, int32_t B, uint64_t seed, uint64_t first_index, int32_t steps, int32_t obs_motion,

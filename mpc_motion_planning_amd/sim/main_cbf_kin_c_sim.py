@@ -1,11 +1,14 @@
 """Closed-loop simulation, one static obstacle — counterpart of
 CasaDi_MPC_Optimize_Multishoot/main_cbf_kin_c_sim.py (same scene constants :45,49,55,68, same loop :87-123).
 
-    python -m mpc_motion_planning_amd.sim.main_cbf_kin_c_sim [--device-loop] [--aa 0.5] [--out run.npz]
+    python -m mpc_motion_planning_amd.sim.main_cbf_kin_c_sim [--device-loop | --external-plant] [--aa 0.5] [--out run.npz]
 
 Default: the reference's flow step by step through the drop-in surface (optimize_problem -> solver -> shift_movement).
 --device-loop: the same 80 steps inside one mpcb_closed_loop call (no host round trips).  Figures are out of scope;
 the histories go to an .npz file.
+--external-plant: the driver's batch (one instance) through ControlLoop.step: the controller's warm start stays on the device, the
+plant step and the obstacle advance are done here in numpy (stand-ins for the caller's own simulator and perception); only x0, xs, the
+obstacle rows and U_0 cross PCIe.  This is the integration example of INTEGRATION.md, "your simulator in the loop".
 --aa: blend weight of the reference path window in the stage cost (kin.py:194-199; the reference ships 0.0).
 """
 import argparse
@@ -20,6 +23,7 @@ from mpc_motion_planning_amd.helpers import load_config, find_params_file
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--device-loop", action="store_true")
+    ap.add_argument("--external-plant", action="store_true", help="ControlLoop.step with the plant and the obstacle advance in numpy")
     ap.add_argument("--out", default=None)
     ap.add_argument("--sim-time", type=float, default=8.0)
     ap.add_argument("--aa", type=float, default=0.0, help="path-tracking blend weight in [0, 1] (0: set-point only)")
@@ -41,6 +45,24 @@ def main(argv=None):
         r = bs.closed_loop(x0.T, xs.T, obs[None], steps=steps, aa=args.aa)   # obstacles stay put, as in the reference's loop
         print("device loop: %d steps in %.1f ms, statuses %s" % (steps, 1e3 * (time.time() - t0), np.bincount(r["status"][0], minlength=5)))
         xh, uh = r["x_hist"][0], r["u_hist"][0]
+    elif args.external_plant:
+        if args.aa != 0.0:
+            ap.error("--external-plant runs the set-point loop (build x_ref rows yourself for tracking)")
+        bs = mpc._batch_solver(mpc._make_cfg(1))
+        xc, xsb, oc = x0.T.copy(), xs.T.copy(), obs[None].copy()
+        xh, uh, st, t0 = [xc[0].copy()], [], [], time.time()
+        with bs.loop(1, hold_on_failure=True) as loop:
+            for _ in range(steps):
+                r = loop.step(xc, xsb, oc)
+                u = r["u0"]
+                # the caller's plant: here the model's own right-hand side, one Euler step (main_cbf_kin_c_sim.py:17-18)
+                f = np.stack([xc[:, 3] * np.cos(xc[:, 2]), xc[:, 3] * np.sin(xc[:, 2]), xc[:, 3] * np.tan(u[:, 0]) / bs.cfg.veh_l, u[:, 1]], axis=1)
+                xc = xc + T_S * f
+                # the caller's perception: the reference's loop leaves the obstacle where it is (oc unchanged)
+                uh.append(u[0].copy()); xh.append(xc[0].copy()); st.append(int(r["status"][0]))
+            fails = int(loop.failures[0])
+        print("external plant: %d steps in %.1f ms, statuses %s, held steps %d" % (steps, 1e3 * (time.time() - t0), np.bincount(st, minlength=5), fails))
+        xh, uh = np.array(xh), np.array(uh)
     else:
         ref = RefPathGenerator.RefPathGenerator()
         ref.define_ref_path(x0, xs, T_S)

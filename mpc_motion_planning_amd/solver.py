@@ -143,6 +143,110 @@ class DeviceArray:
         self.ptr = None
 
 
+def _devptr(v):
+    """c_void_p of a DeviceArray / int / c_void_p (None stays None)."""
+    if v is None:
+        return None
+    if isinstance(v, DeviceArray):
+        return v.ptr
+    return v if isinstance(v, C.c_void_p) else C.c_void_p(int(v))
+
+
+class ControlLoop:
+    """One receding-horizon controller for B instances whose state (warm start, counters) stays on the device between steps
+    (mpcb_loop_create); made by BatchSolver.loop.  The caller steps its own plant: `step` takes this step's states, set-points,
+    obstacles and (optionally) stage references and returns the control to apply.  close() it (or use it as a context manager)
+    before the solver; closing the solver first is safe as well."""
+
+    def __init__(self, solver, ptr, B, hold_on_failure, predict, params):
+        self.solver, self.ptr, self.B = solver, ptr, int(B)
+        self.hold_on_failure, self.predict, self.params = bool(hold_on_failure), bool(predict), params
+
+    def close(self):
+        if self.ptr is not None and self.solver._h:
+            check(lib().mpcb_loop_destroy(self.solver._h, self.ptr), self.solver._h)
+        self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def step(self, x0, xs, obs=None, x_ref=None, want_z=True):
+        """x0, xs [B,nx]; obs [B,n_obs,6] | [B,n_obs,N+1,6]; x_ref [B,N,nx] | None  ->  dict(u0 [B,2], status, iters, z, obj).
+        u0 is the first control of the executed plan (with hold_on_failure: of the previous plan where this step's solve failed);
+        z, obj, status and iters are the solve's own.  want_z=False leaves the iterate on the device (z is None): per instance only
+        u0, status, iters and obj come back."""
+        s, B = self.solver, self.B
+        x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64))
+        xs = np.ascontiguousarray(np.asarray(xs, dtype=np.float64))
+        if x0.shape != (B, s.nx) or xs.shape != (B, s.nx):
+            raise ValueError("x0 and xs must be [B,%d] = [%d,%d]" % (s.nx, B, s.nx))
+        if x_ref is not None:
+            x_ref = np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64))
+            if x_ref.shape != (B, s.N, s.nx):
+                raise ValueError("x_ref must be [B,N,nx] = [%d,%d,%d], got %s" % (B, s.N, s.nx, x_ref.shape))
+        obs, kind = s._obs(obs, B)
+        u0 = np.empty((B, 2)); z = np.empty((B, s.nz)) if want_z else None
+        obj = np.empty(B); st = np.empty(B, np.int32); it = np.empty(B, np.int32)
+        check(lib().mpcb_loop_step(s._h, self.ptr, dptr(x0), dptr(xs), dptr(x_ref), dptr(obs), kind, dptr(u0), iptr(st), iptr(it), dptr(z),
+                                   dptr(obj)), s._h)
+        return dict(u0=u0, status=st, iters=it, z=z, obj=obj)
+
+    def step_device(self, d_x0, d_xs, d_u0, d_obs=None, obs_kind=_abi.OBSIN_STATIC, d_x_ref=None, d_status=None, d_iters=None, d_z=None,
+                    d_obj=None, sync=False):
+        """step on device buffers (DeviceArray / raw pointers), asynchronous on the loop's lane unless sync."""
+        s = self.solver
+        check(lib().mpcb_loop_step_device(s._h, self.ptr, _devptr(d_x0), _devptr(d_xs), _devptr(d_x_ref), _devptr(d_obs), int(obs_kind),
+                                          _devptr(d_u0), _devptr(d_status), _devptr(d_iters), _devptr(d_z), _devptr(d_obj), 1 if sync else 0), s._h)
+
+    def advance_device(self, d_x0, d_u0, d_obs=None, first_only=False, sync=False):
+        """The library's plant step d_x0 <- d_x0 + T f(d_x0, d_u0) and one constant-velocity step of the obstacles in d_obs [B,n_obs,6]
+        (first_only: of obstacle 0 alone; None: of none), on the loop's lane: the other half of closed_loop's step."""
+        s = self.solver
+        check(lib().mpcb_loop_advance_device(s._h, self.ptr, _devptr(d_x0), _devptr(d_u0), _devptr(d_obs),
+                                             _abi.CL_ADVANCE_FIRST_ONLY if first_only else 0, 1 if sync else 0), s._h)
+
+    def reset(self, mask=None):
+        """Warm start and counters back to zero: every instance, or those where mask [B] is true (an episode restarts)."""
+        if mask is not None:
+            mask = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.int32)
+            if mask.shape != (self.B,):
+                raise ValueError("mask must be [B] = [%d]" % self.B)
+        check(lib().mpcb_loop_reset(self.solver._h, self.ptr, iptr(mask)), self.solver._h)
+
+    @property
+    def start(self):
+        """The warm start [B,nz] the next step solves from (the executed plan shifted one stage; zero after create / reset)."""
+        w = np.empty((self.B, self.solver.nz))
+        check(lib().mpcb_loop_get_start(self.solver._h, self.ptr, dptr(w)), self.solver._h)
+        return w
+
+    @start.setter
+    def start(self, w):
+        w = np.ascontiguousarray(np.asarray(w, dtype=np.float64))
+        if w.shape != (self.B, self.solver.nz):
+            raise ValueError("start must be [B,nz] = [%d,%d], got %s" % (self.B, self.solver.nz, w.shape))
+        check(lib().mpcb_loop_set_start(self.solver._h, self.ptr, dptr(w)), self.solver._h)
+
+    def _counters(self):
+        n = np.empty(self.B, np.int32); f = np.empty(self.B, np.int32)
+        check(lib().mpcb_loop_counters(self.solver._h, self.ptr, iptr(n), iptr(f)), self.solver._h)
+        return n, f
+
+    @property
+    def steps(self):
+        """Steps per instance since the last reset [B]."""
+        return self._counters()[0]
+
+    @property
+    def failures(self):
+        """Steps per instance since the last reset whose solve ended neither solved nor acceptable [B]."""
+        return self._counters()[1]
+
+
 class BatchSolver:
     def __init__(self, cfg, device=0, inflight=1):
         """inflight: launch lanes of the handle (mpcb_set_inflight).  With k > 1 consecutive asynchronous `solve_device` calls
@@ -220,6 +324,16 @@ class BatchSolver:
             raise ValueError("parameter set rejected, first bad row %d: %s" % (bad.value, msg.decode("utf-8", "replace") if msg else ""))
         check(rc, self._h)
         return ParamSet(self, p, B)
+
+    def loop(self, B, hold_on_failure=False, predict=False, params=None):
+        """A ControlLoop of B instances (mpcb_loop_create): the receding-horizon controller one step at a time, for a plant, obstacles
+        and episode ends that are the caller's.  hold_on_failure: a step whose solve fails applies and keeps the previous plan.
+        predict: static obstacle rows [B,n_obs,6] given to a step are rolled out at constant velocity over the horizon before the solve.
+        params: a ParamSet of B rows, instance b is solved (and advanced by advance_device) under row b."""
+        flags = (_abi.CL_HOLD_ON_FAILURE if hold_on_failure else 0) | (_abi.LOOP_PREDICT if predict else 0)
+        p = C.c_void_p()
+        check(lib().mpcb_loop_create(self._h, int(B), flags, params.ptr if params is not None else None, C.byref(p)), self._h)
+        return ControlLoop(self, p, B, hold_on_failure, predict, params)
 
     def solve_batch(self, x0, xs, obs=None, z0=None, multipliers=False, x_ref=None, params=None):
         """x0, xs [B,nx]; obs [B,n_obs,6] | [B,n_obs,N+1,6]; z0 [B,nz] | None  ->  dict(z, obj, status, iters, kkt[, lam_g, lam_x])
