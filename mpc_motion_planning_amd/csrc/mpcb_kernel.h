@@ -317,6 +317,9 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
   static_assert(!PARAMS || (!GEN && !RK4 && !TRACK && NOBS <= 3), "per-instance configs: Euler, keep-out / gamma = 1 rows, up to 3 obstacles, no tracking");
   using namespace mpcbk;
   constexpr int NX = 4, NA = 6, NW = 8, NOB = NOBS > 0 ? NOBS : 1, NEL = RESTO ? NOB : 1;
+  // the forward roll-out passes its six numbers by DPP row broadcasts instead of scalar registers (see there) in the first-pass Euler
+  // kernels of up to 3 obstacle rows and their TRACK / PARAMS twins; every other instantiation keeps the v_readlane form
+  constexpr bool ROW_ROLLOUT = !RESTO && !GEN && !RK4 && NOBS <= 3;
   const mpcb_config* cp_ = &a.cfg;
   if constexpr (PARAMS) cp_ = wv::late_row(a.cfgs, b);           // row b of the parameter set: uniform, constant address space
   const mpcb_config& c = *cp_;
@@ -1382,12 +1385,14 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
       // ----- forward roll-out of the step: lane i < 6 advances component i of [dX_s; dU_{s-1}] ---------------------
       // One stage is  t_i = c_i0 + sum_r C_ir v_r  (rows 0..3: the A part of the state update plus the defect, rows 4, 5: the gain
       // rows, t = dU_s), then  n_i = t_i + b_i0 dU_s[0] + b_i1 dU_s[1]  (the B part: b20 in row 2, T_s in row 3).  The six numbers
-      // of v travel through scalar registers (v_readlane); a lane reads the nine numbers of its own record of the stage's fw row
+      // of v travel through scalar registers (v_readlane; ROW_ROLLOUT: by DPP row broadcasts, see below); a lane reads the nine numbers of its own record of the stage's fw row
       // instead of every lane reading the whole row, and the steps are written to the rows of the (spent) condensed gradient, [component][node], where lane k picks up its node's.
       double dX[NX] = {0, 0, 0, 0}, dU[NU] = {0, 0};
       {
         const int lq = wv::opaque(lane);                 // (addresses re-formed per iteration instead of staying live — and spilled — through the solve)
-        const int li = lq < NA ? lq : 0;
+        // ROW_ROLLOUT: lanes 0..5 of EVERY 16-lane row run the six components (the rows repeat row 0 number for number), so that a
+        // component reaches the lanes of its row by a row broadcast (one v_mov_b64 DPP) instead of two v_readlane and a scalar operand
+        const int li = ROW_ROLLOUT ? ((lq & 15) < NA ? (lq & 15) : 0) : (lq < NA ? lq : 0);
         // rows 0..3 hold dX_{s+1}, rows 4, 5 hold dU_s; the other lanes store into the two remaining (equally spent) gradient rows,
         // so that the store needs no EXEC change
         double* hist = ent + (E_G0 + (lq < NA ? lq : NA + (lq & 1))) * ld + (lq < NX ? 1 : 0);
@@ -1399,15 +1404,16 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
           for (int r = 0; r < NA; ++r) f.c[r] = q[r];
           f.c0 = q[FW_C0]; f.bx = q[FW_BX];
         };
-        double v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0;           // wave-uniform
+        double v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0;           // wave-uniform (ROW_ROLLOUT: per lane, equal in all lanes)
         auto fstage = [&](int s, const FwRec& f, FwRec& nxt) {
           load_fw(s + 1, nxt);                             // (row N exists and holds finite numbers; its record is never used)
           MPCB_SCHED_FENCE();
           double t, du0, du1, n;
           if (!RK4) {
             t = fma(f.c[5], v5, fma(f.c[4], v4, fma(f.c[3], v3, fma(f.c[2], v2, fma(f.c[1], v1, fma(f.c[0], v0, f.c0))))));
-            du0 = wv::bcast(t, NX); du1 = wv::bcast(t, NX + 1);
-            n = fma(f.bx, lq == 3 ? du1 : du0, t);      // the control enters row 2 (b20 dU[0]) and row 3 (T dU[1])
+            if constexpr (ROW_ROLLOUT) { du0 = wv::row_bcast<NX>(v4, t); du1 = wv::row_bcast<NX + 1>(v5, t); }
+            else { du0 = wv::bcast(t, NX); du1 = wv::bcast(t, NX + 1); }
+            n = fma(f.bx, (ROW_ROLLOUT ? (lq & 15) == 3 : lq == 3) ? du1 : du0, t);      // the control enters row 2 (b20 dU[0]) and row 3 (T dU[1])
           } else {
             // slots 4, 5 of a state row's record hold its two control coefficients (dense B), of a gain row's the U_prev coefficients
             const double tx = fma(f.c[3], v3, fma(f.c[2], v2, fma(f.c[1], v1, fma(f.c[0], v0, f.c0))));
@@ -1416,7 +1422,9 @@ MPCB_DEVFN void mpcb_solve_kin(const MpcbKArgs& a_in, const int b, double* lds, 
             n = lq < NX ? fma(f.c[5], du1, fma(f.c[4], du0, t)) : t;
           }
           hist[s] = n;
-          v0 = wv::bcast(n, 0); v1 = wv::bcast(n, 1); v2 = wv::bcast(n, 2); v3 = wv::bcast(n, 3); v4 = du0; v5 = du1;
+          if constexpr (ROW_ROLLOUT) { v0 = wv::row_bcast<0>(v0, n); v1 = wv::row_bcast<1>(v1, n); v2 = wv::row_bcast<2>(v2, n); v3 = wv::row_bcast<3>(v3, n); }
+          else { v0 = wv::bcast(n, 0); v1 = wv::bcast(n, 1); v2 = wv::bcast(n, 2); v3 = wv::bcast(n, 3); }
+          v4 = du0; v5 = du1;
         };
         {
           FwRec fA, fB;

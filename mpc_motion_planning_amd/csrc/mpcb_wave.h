@@ -75,6 +75,14 @@ template <int CTRL> MPCB_DEV double dpp_mov(double v) {
   hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
   return __hiloint2double(hi, lo);
 }
+// value of lane SRC of the caller's own 16-lane row in every lane of that row: ONE v_mov_b64 with the row_newbcast DPP control (the only
+// control 64-bit DPP takes), against two v_readlane and a scalar operand for bcast.  `dead` is any double that is not needed any more:
+// the result takes its registers (every lane is written, so its value is never seen); without it the compiler clears or copies a
+// register pair in front of every broadcast.
+template <int SRC> MPCB_DEV double row_bcast(double dead, double v) {
+  static_assert(SRC >= 0 && SRC < 16, "a row has 16 lanes");
+  return __builtin_amdgcn_update_dpp(dead, v, 0x150 + SRC, 0xF, 0xF, false);
+}
 template <int NS, int NM> MPCB_DEV void reduce(double* s, double* m) {
 #define MPCB_STEP(EXPR)                                                        \
   {                                                                            \
@@ -176,6 +184,10 @@ inline bool all(bool p) { return sum(p ? 0.0 : 1.0) == 0.0; }
 template <int NS, int NM> inline void reduce(double* s, double* m) {
   for (int i = 0; i < NS; ++i) s[i] = sum(s[i]);
   for (int i = 0; i < NM; ++i) m[i] = max(m[i]);
+}
+template <int SRC> inline double row_bcast(double, double v) {
+  static_assert(SRC >= 0 && SRC < 16, "a row has 16 lanes");
+  return shfl(v, (t_lane & ~15) | SRC);
 }
 inline int opaque(int v) { return v; }
 template <class T> inline const T* late_args(const T& a) { return &a; }
