@@ -392,6 +392,47 @@ int mpcb_loop_step_device(mpcb_handle* h, mpcb_loop* L,
                           double* d_u0, int32_t* d_status, int32_t* d_iters, double* d_z, double* d_obj, int32_t sync);
 int mpcb_loop_advance_device(mpcb_handle* h, mpcb_loop* L, double* d_x0, const double* d_u0, double* d_obs, int32_t flags, int32_t sync);
 
+/* ---- evaluate and certify any point: NLP functions and KKT residuals --------------------------------------------------------------
+ * What the NLP (the one mpcb_solve solves, in the library's own row form and order: the rows lam_g refers to) says about a point z that
+ * need not come from a solve: a held-and-shifted plan, a warm start, a learned policy's trajectory, a plan re-checked against newer
+ * obstacle predictions.  Nothing of the solver's scaling or elimination enters.  One wavefront per instance, no iteration.
+ *   z      [B, nz]  the point (required)
+ *   lam_g  [B, ng], lam_x [B, nz]  multipliers in IPOPT's sign convention (what mpcb_solve returns): both or neither
+ *   x_ref  [B, N, nx] or NULL: the tracking objective of mpcb_solve_ref (kinematic model, no set)
+ *   p      NULL, or a live parameter set of h: instance b is evaluated under row b.  Anything mpcb_params_create accepted is evaluated;
+ *          the restrictions of mpcb_solve_params (gamma, MPCB_INT_RK4, n_obs > 3) do not apply.
+ * outputs (each may be NULL):
+ *   obj [B]          the objective (kin.py:195-205; with x_ref the tracking objective)
+ *   g [B, ng]        the constraint vector, res['g'] of the reference: obstacle rows are h on both models, or
+ *                    gamma h_i(X_i) + h_i(X_{i+1}) - h_i(X_i) for MPCB_OBS_DCBF
+ *   grad_lag [B, nz] grad f + J_g' lam_g + lam_x, from closed-form transposed Jacobians; needs the multipliers
+ *   res [B, MPCB_EVAL_COLS] = { feas_g       max violation of lbg <= g <= ubg (the handle's bounds, unrelaxed),
+ *                               feas_x       max violation of lbx <= z <= ubx,
+ *                               h_min        smallest ellipse value h_j(X_k) over k = 0..N and all obstacles, each with that node's obstacle
+ *                                            row, whatever the row mode: negative inside a keep-out ellipse, +inf for n_obs = 0,
+ *                               stationarity max |grad_lag|,
+ *                               compl        max over rows and boxes of lam * distance to the bound lam points at,
+ *                               sign         largest multiplier that points at a bound that does not exist,
+ *                               lam_scale    max(1, max |lam_g|, max |lam_x|) };  the last four are NaN without multipliers
+ *                    A NaN in z or in a multiplier is never dropped: every column it enters is NaN (compl, sign and lam_scale too), so
+ *                    no comparison against a tolerance passes for that instance.
+ * Refused before anything is launched: z NULL, one multiplier array without the other, grad_lag without multipliers (MPCB_E_INVALID);
+ * x_ref on MPCB_MODEL_DYN or together with a set, a time grid (mpcb_set_time_grid), a device group (MPCB_E_UNSUPPORTED).
+ * mpcb_evaluate takes host pointers, waits for the lanes and runs on the handle's stream.  mpcb_evaluate_device takes device pointers and
+ * is queued on the lane that took the handle's most recent mpcb_solve_device* call, behind it (lane 0 with one lane or before any solve);
+ * it does not advance the rotation of mpcb_set_inflight, so (solve, evaluate) pairs on rotated buffers overlap as the solves alone do. */
+#define MPCB_EVAL_COLS 7
+int mpcb_evaluate(mpcb_handle* h, int32_t B, const mpcb_params* p,
+                  const double* x0, const double* xs, const double* x_ref,
+                  const double* obs, int32_t obs_kind, const double* z,
+                  const double* lam_g, const double* lam_x,
+                  double* obj, double* g, double* grad_lag, double* res);
+int mpcb_evaluate_device(mpcb_handle* h, int32_t B, const mpcb_params* p,
+                         const double* d_x0, const double* d_xs, const double* d_x_ref,
+                         const double* d_obs, int32_t obs_kind, const double* d_z,
+                         const double* d_lam_g, const double* d_lam_x,
+                         double* d_obj, double* d_g, double* d_grad_lag, double* d_res, int32_t sync);
+
 /* ---- scene generation on the device -----------------------------------------------------------------------
  * Counter-based random scenes (Philox4x32-10 keyed by `seed`, counter = global scene index): scene i is the same whichever GPU,
  * batch or chunk it is generated in, so 8 GPUs draw disjoint slices of one Monte-Carlo population from (seed, first_index).

@@ -19,6 +19,7 @@
 
 #include "mpcb_kernel_dyn.h"
 #include "mpcb_dispatch.h"
+#include "mpcb_eval.h"
 
 #ifndef MPCB_WAVES_PER_SIMD
 #define MPCB_WAVES_PER_SIMD 1
@@ -158,6 +159,15 @@ template <int NOBS>
 __global__ __launch_bounds__(64, 1) void mpcb_param_dyn_resto(const MpcbKArgs a) {
   extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
   mpcb_solve_dyn<NOBS, true, true>(a, (int)blockIdx.x, mpcb_lds, MPCB_PASS_RESTO);
+}
+
+// Evaluation of the NLP at a point (mpcb_evaluate): one wave per instance, the structure read from the config at run time, so there is one
+// kernel per model and per source of the config.  (Inside this namespace the name is the kernel's; the device function of mpcb_eval.h is
+// ::mpcb_eval.)
+template <int NX, bool PARAMS>
+__global__ __launch_bounds__(64) void mpcb_eval(const MpcbEvalArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
+  ::mpcb_eval<NX, PARAMS>(a, (int)blockIdx.x, mpcb_lds);
 }
 
 // f(x,u) of the configured model: the reference's `mpc_solver.f` (kin.py:153-159, dyn.py:156-177); host and device
@@ -598,6 +608,7 @@ struct mpcb_handle {
   struct Lane { hipStream_t stream = nullptr; double* d_work = nullptr; int32_t* d_st_own = nullptr; int work_cap = 0; hipEvent_t done = nullptr; bool busy = false; };
   std::vector<Lane> lanes;                             // lanes[0].stream == stream
   int next_lane = 0;
+  int last_solve_lane = 0;                             // the lane that took the most recent mpcb_solve_device* call: mpcb_evaluate_device queues behind it
   hipEvent_t ev_fork = nullptr;                        // "everything queued so far on the handle's stream", awaited by a lane before it launches
   std::vector<std::vector<hipEvent_t>> marks;          // mpcb_event_record: per slot one event per lane stream
   std::vector<double> tgrid_host;                      // host copy of the time grid (handed to the peers of a device group)
@@ -777,7 +788,7 @@ int ensure_lanes(mpcb_handle* h, int k) {
     h->lanes.push_back(L);
   }
   if (!h->ev_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-  h->next_lane = 0;
+  h->next_lane = 0; h->last_solve_lane = 0;
   return MPCB_OK;
 }
 
@@ -931,6 +942,7 @@ int solve_next_lane(mpcb_handle* h, const SolveArgs& s, int32_t sync) {
   const int K = h->lanes.empty() ? 1 : (int)h->lanes.size();
   const int lane = K == 1 ? 0 : h->next_lane;
   if (K > 1) h->next_lane = (h->next_lane + 1) % K;
+  h->last_solve_lane = lane;
   int rc = solve_on_device(h, s, lane);
   if (rc != MPCB_OK) return rc;
   return sync ? mpcb_sync(h) : MPCB_OK;
@@ -990,6 +1002,56 @@ int check_params_use(mpcb_handle* h, const mpcb_params* p, int32_t B) {
   if (h->d_tgrid) return fail(h, MPCB_E_UNSUPPORTED, "parameter sets do not run with a time grid (mpcb_set_time_grid): T is structural");
   const char* field = structural_diff(p->base, h->cfg);          // mpcb_set_bounds after mpcb_params_create may have changed the row pattern
   if (field) return fail(h, MPCB_E_INVALID, "the handle's %s changed since the parameter set was created", field);
+  return MPCB_OK;
+}
+
+// ---- evaluation of a point ---------------------------------------------------------------------------------------------------------
+// The pointers of one evaluation in the order the C entries list them (device pointers for eval_on_device, the caller's host pointers in
+// mpcb_evaluate); cfgs: the rows of a parameter set on the device, NULL = the handle's config.
+struct EvalArgs {
+  int32_t B = 0; const mpcb_config* cfgs = nullptr; const double *x0 = nullptr, *xs = nullptr, *xref = nullptr, *obs = nullptr; int32_t obs_kind = MPCB_OBSIN_STATIC;
+  const double *z = nullptr, *lam_g = nullptr, *lam_x = nullptr; double *obj = nullptr, *g = nullptr, *grad = nullptr, *res = nullptr;
+};
+
+// every refusal of mpcb_evaluate / mpcb_evaluate_device: before anything is uploaded or launched
+int check_eval(mpcb_handle* h, const mpcb_params* p, const EvalArgs& e) {
+  if (p) { int rc = check_params_use(h, p, e.B); if (rc != MPCB_OK) return rc; }
+  if (e.B < 0 || !e.x0 || !e.xs) return fail(h, MPCB_E_INVALID, p ? "a required pointer is NULL" : "B < 0 or a required pointer is NULL");
+  if (!e.z) return fail(h, MPCB_E_INVALID, "z is NULL: there is no point to evaluate");
+  if ((e.lam_g != nullptr) != (e.lam_x != nullptr)) return fail(h, MPCB_E_INVALID, "lam_g and lam_x: both or neither (%s is NULL)", e.lam_g ? "lam_x" : "lam_g");
+  if (e.grad && !e.lam_g) return fail(h, MPCB_E_INVALID, "grad_lag needs the multipliers lam_g and lam_x");
+  if (h->cfg.n_obs > 0 && !e.obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
+  if (e.obs_kind != MPCB_OBSIN_STATIC && e.obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", e.obs_kind);
+  if (e.xref && h->cfg.model == MPCB_MODEL_DYN) return fail(h, MPCB_E_UNSUPPORTED, "per-stage reference tracking is built for the kinematic model only");
+  if (e.xref && p) return fail(h, MPCB_E_UNSUPPORTED, "a parameter set together with a per-stage reference");
+  {  // the kernel places its rows by mk_bnd's predicate (a rate row where a bound is inside +-1e300), the handle's ng counts std::isfinite
+     // bounds: they differ for du_lo = +inf, du_hi = -inf or |bound| >= 1e300, and the rows of g would then not be where lam_g has them
+    int by_kernel = 0;
+    for (int i = 0; i < 2; ++i) if (h->cfg.du_lo[i] > -1e300 || h->cfg.du_hi[i] < 1e300) ++by_kernel;
+    if (by_kernel != n_rate(h->cfg)) return fail(h, MPCB_E_INVALID, "du_lo / du_hi: a rate bound that is neither a number below 1e300 in size nor the infinity of its side");
+  }
+  if (h->d_tgrid) return fail(h, MPCB_E_UNSUPPORTED, "the evaluation does not run with a time grid (mpcb_set_time_grid)");
+  if (!h->peers.empty()) return fail(h, MPCB_E_UNSUPPORTED, "the evaluation does not run on a device group (mpcb_set_devices)");
+  return MPCB_OK;
+}
+
+// one launch of the evaluation over B instances on `stream`, everything resident on the handle's device.  The LDS of a workgroup is what
+// mpcbk::layout_eval says for the handle's nz and ng: at most 2 * 510 + 2 * 1020 + 510 doubles (N = 63, dynamic model, 8 obstacles), 28 KiB.
+int launch_eval(mpcb_handle* h, hipStream_t stream, const EvalArgs& e) {
+  if (e.B == 0) return MPCB_OK;
+  MpcbEvalArgs a;
+  a.cfg = h->cfg; a.cfgs = e.cfgs; a.B = e.B; a.nz = h->nz; a.ng = h->ng; a.obs_kind = e.obs_kind;
+  a.x0 = e.x0; a.xs = e.xs; a.xref = e.xref; a.obs = e.obs; a.z = e.z; a.lam_g = e.lam_g; a.lam_x = e.lam_x;
+  a.obj = e.obj; a.g = e.g; a.grad = e.grad; a.res = e.res;
+  const size_t lds = (size_t)mpcbk::layout_eval(h->nz, h->ng).total * sizeof(double);
+  if (h->nx == 6) {
+    if (e.cfgs) hipLaunchKernelGGL((mpcb_eval<6, true>), dim3(e.B), dim3(64), lds, stream, a);
+    else hipLaunchKernelGGL((mpcb_eval<6, false>), dim3(e.B), dim3(64), lds, stream, a);
+  } else {
+    if (e.cfgs) hipLaunchKernelGGL((mpcb_eval<4, true>), dim3(e.B), dim3(64), lds, stream, a);
+    else hipLaunchKernelGGL((mpcb_eval<4, false>), dim3(e.B), dim3(64), lds, stream, a);
+  }
+  HIP_TRY(h, hipGetLastError());
   return MPCB_OK;
 }
 
@@ -1684,6 +1746,75 @@ int mpcb_closed_loop_params(mpcb_handle* h, int32_t B, int32_t steps, const mpcb
   { int rc = check_params_use(h, p, B); if (rc != MPCB_OK) return rc; }
   return closed_loop_impl(h, B, steps, x0, xs, obs_state, obs_motion, flags, x_hist, u_hist, status_hist, iters_hist, 0, 0, 0, nullptr, nullptr,
                           false, 0.0, p->d_cfgs);
+}
+
+// ---- evaluate and certify a point --------------------------------------------------------------------------------------------------
+int mpcb_evaluate_device(mpcb_handle* h, int32_t B, const mpcb_params* p, const double* d_x0, const double* d_xs, const double* d_x_ref,
+                         const double* d_obs, int32_t obs_kind, const double* d_z, const double* d_lam_g, const double* d_lam_x, double* d_obj,
+                         double* d_g, double* d_grad_lag, double* d_res, int32_t sync) {
+  if (!h) return MPCB_E_INVALID;
+  EvalArgs e;
+  e.B = B; e.x0 = d_x0; e.xs = d_xs; e.xref = d_x_ref; e.obs = d_obs; e.obs_kind = obs_kind; e.z = d_z; e.lam_g = d_lam_g; e.lam_x = d_lam_x;
+  e.obj = d_obj; e.g = d_g; e.grad = d_grad_lag; e.res = d_res;
+  { int rc = check_eval(h, p, e); if (rc != MPCB_OK) return rc; }
+  e.cfgs = p ? p->d_cfgs : nullptr;
+  HIP_TRY(h, hipSetDevice(h->device));
+  // behind the most recent asynchronous solve, on its lane; the rotation of mpcb_set_inflight is not advanced
+  const int K = h->lanes.empty() ? 1 : (int)h->lanes.size();
+  const int lane = h->last_solve_lane < K ? h->last_solve_lane : 0;
+  { int rc = lane_follows_handle(h, lane); if (rc != MPCB_OK) return rc; }
+  { int rc = launch_eval(h, h->lanes[lane].stream, e); if (rc != MPCB_OK) return rc; }
+  { int rc = lane_done(h, lane); if (rc != MPCB_OK) return rc; }
+  return sync ? mpcb_sync(h) : MPCB_OK;
+}
+
+int mpcb_evaluate(mpcb_handle* h, int32_t B, const mpcb_params* p, const double* x0, const double* xs, const double* x_ref, const double* obs,
+                  int32_t obs_kind, const double* z, const double* lam_g, const double* lam_x, double* obj, double* g, double* grad_lag,
+                  double* res) {
+  if (!h) return MPCB_E_INVALID;
+  EvalArgs in;
+  in.B = B; in.x0 = x0; in.xs = xs; in.xref = x_ref; in.obs = obs; in.obs_kind = obs_kind; in.z = z; in.lam_g = lam_g; in.lam_x = lam_x;
+  in.obj = obj; in.g = g; in.grad = grad_lag; in.res = res;
+  { int rc = check_eval(h, p, in); if (rc != MPCB_OK) return rc; }
+  if (B == 0) return MPCB_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
+  const size_t nx = h->nx, nz = h->nz, ng = h->ng, N = h->cfg.N, nb = (size_t)B;
+  const size_t n_obs_d = nb * h->cfg.n_obs * 6 * (obs_kind == MPCB_OBSIN_PREDICTED ? N + 1 : 1);
+  EvalArgs d = in;
+  d.cfgs = p ? p->d_cfgs : nullptr;
+  double *d_x0, *d_xs, *d_xr, *d_obs, *d_z, *d_lg, *d_lx;
+  auto carve = [&](Carve& cv) {
+    d_x0 = cv.take<double>(nb * nx);
+    d_xs = cv.take<double>(nb * nx);
+    d_xr = x_ref ? cv.take<double>(nb * N * nx) : nullptr;
+    d_obs = n_obs_d ? cv.take<double>(n_obs_d) : nullptr;
+    d_z = cv.take<double>(nb * nz);
+    d_lg = lam_g ? cv.take<double>(nb * ng) : nullptr;
+    d_lx = lam_x ? cv.take<double>(nb * nz) : nullptr;
+    d.obj = obj ? cv.take<double>(nb) : nullptr;
+    d.g = g ? cv.take<double>(nb * ng) : nullptr;
+    d.grad = grad_lag ? cv.take<double>(nb * nz) : nullptr;
+    d.res = res ? cv.take<double>(nb * MPCB_EVAL_COLS) : nullptr;
+  };
+  { Carve dry{nullptr}; carve(dry); int rc = ensure_scratch(h, dry.bytes()); if (rc != MPCB_OK) return rc; }
+  { Carve cv{(char*)h->d_buf}; carve(cv); }
+  d.x0 = d_x0; d.xs = d_xs; d.xref = d_xr; d.obs = d_obs; d.z = d_z; d.lam_g = d_lg; d.lam_x = d_lx;
+  hipStream_t s = h->stream;
+  HIP_TRY(h, hipMemcpyAsync(d_x0, x0, nb * nx * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(d_xs, xs, nb * nx * 8, hipMemcpyHostToDevice, s));
+  if (d_xr) HIP_TRY(h, hipMemcpyAsync(d_xr, x_ref, nb * N * nx * 8, hipMemcpyHostToDevice, s));
+  if (d_obs) HIP_TRY(h, hipMemcpyAsync(d_obs, obs, n_obs_d * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(d_z, z, nb * nz * 8, hipMemcpyHostToDevice, s));
+  if (d_lg) HIP_TRY(h, hipMemcpyAsync(d_lg, lam_g, nb * ng * 8, hipMemcpyHostToDevice, s));
+  if (d_lx) HIP_TRY(h, hipMemcpyAsync(d_lx, lam_x, nb * nz * 8, hipMemcpyHostToDevice, s));
+  { int rc = launch_eval(h, s, d); if (rc != MPCB_OK) return rc; }
+  if (obj) HIP_TRY(h, hipMemcpyAsync(obj, d.obj, nb * 8, hipMemcpyDeviceToHost, s));
+  if (g) HIP_TRY(h, hipMemcpyAsync(g, d.g, nb * ng * 8, hipMemcpyDeviceToHost, s));
+  if (grad_lag) HIP_TRY(h, hipMemcpyAsync(grad_lag, d.grad, nb * nz * 8, hipMemcpyDeviceToHost, s));
+  if (res) HIP_TRY(h, hipMemcpyAsync(res, d.res, nb * MPCB_EVAL_COLS * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return MPCB_OK;
 }
 
 // ---- the stepwise loop: controller state on the device, plant outside -------------------------------------------------------------

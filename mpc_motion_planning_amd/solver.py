@@ -485,6 +485,44 @@ class BatchSolver:
             check(lib().mpcb_solve_device_ref(self._h, B, p(d_x0), p(d_xs), p(d_x_ref), p(d_obs), obs_kind, p(d_z0), p(d_z), p(d_obj),
                                               p(d_status), p(d_iters), p(d_kkt), p(d_lam_g), p(d_lam_x), 1 if sync else 0), self._h)
 
+    # ----- evaluate and certify a point (include/mpcbatch.h, "evaluate and certify any point") -------------------------
+    def evaluate(self, x0, xs, obs, z, lam_g=None, lam_x=None, x_ref=None, params=None, want_g=True, want_grad=False):
+        """What the NLP says about the points z [B,nz], solved or not (mpcb_evaluate): dict(obj [B], g [B,ng] | None, grad_lag [B,nz] | None,
+        feas_g, feas_x, h_min, stationarity, compl, sign, lam_scale [B] each).  lam_g [B,ng] and lam_x [B,nz]: both or neither; without
+        them stationarity, compl, sign and lam_scale are NaN and want_grad is refused by the library.  x_ref [B,N,nx]: the tracking
+        objective (kinematic model).  params: a ParamSet of B rows, instance b is evaluated under row b."""
+        x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
+        xs = np.ascontiguousarray(np.atleast_2d(np.asarray(xs, dtype=np.float64)))
+        B = x0.shape[0]
+        if x0.shape != (B, self.nx) or xs.shape != (B, self.nx):
+            raise ValueError("x0 and xs must be [B,%d]" % self.nx)
+        if x_ref is not None:
+            x_ref = np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64))
+            if x_ref.shape != (B, self.N, self.nx):
+                raise ValueError("x_ref must be [B,N,nx] = [%d,%d,%d], got %s" % (B, self.N, self.nx, x_ref.shape))
+        obs, kind = self._obs(obs, B)
+        z = np.ascontiguousarray(np.asarray(z, dtype=np.float64).reshape(B, self.nz))
+        if lam_g is not None:
+            lam_g = np.ascontiguousarray(np.asarray(lam_g, dtype=np.float64).reshape(B, self.ng))
+        if lam_x is not None:
+            lam_x = np.ascontiguousarray(np.asarray(lam_x, dtype=np.float64).reshape(B, self.nz))
+        obj = np.empty(B); res = np.empty((B, _abi.EVAL_COLS))
+        g = np.empty((B, self.ng)) if want_g else None
+        grad = np.empty((B, self.nz)) if want_grad else None
+        check(lib().mpcb_evaluate(self._h, B, params.ptr if params is not None else None, dptr(x0), dptr(xs), dptr(x_ref), dptr(obs), kind,
+                                  dptr(z), dptr(lam_g), dptr(lam_x), dptr(obj), dptr(g), dptr(grad), dptr(res)), self._h)
+        out = dict(obj=obj, g=g, grad_lag=grad)
+        out.update({name: res[:, i].copy() for i, name in enumerate(_abi.EVAL_NAMES)})
+        return out
+
+    def evaluate_device(self, B, d_x0, d_xs, d_obs, obs_kind, d_z, d_lam_g=None, d_lam_x=None, d_obj=None, d_g=None, d_grad_lag=None,
+                        d_res=None, sync=False, d_x_ref=None, params=None):
+        """mpcb_evaluate_device over raw device pointers (ints / c_void_p / DeviceArray), like solve_device.  Queued behind the handle's most
+        recent solve_device call, on its lane; d_res is [B, 7] in the order of _abi.EVAL_NAMES."""
+        check(lib().mpcb_evaluate_device(self._h, B, params.ptr if params is not None else None, _devptr(d_x0), _devptr(d_xs), _devptr(d_x_ref),
+                                         _devptr(d_obs), obs_kind, _devptr(d_z), _devptr(d_lam_g), _devptr(d_lam_x), _devptr(d_obj), _devptr(d_g),
+                                         _devptr(d_grad_lag), _devptr(d_res), 1 if sync else 0), self._h)
+
     # ----- multi-GPU (include/mpcbatch.h, "multi-GPU") ------------------------------------------------------
     def set_devices(self, ids):
         """One process driving several devices: solve_batch then shards the batch over them and all-gathers z (RCCL)."""
