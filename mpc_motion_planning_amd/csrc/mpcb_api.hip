@@ -20,6 +20,7 @@
 #include "mpcb_kernel_dyn.h"
 #include "mpcb_dispatch.h"
 #include "mpcb_eval.h"
+#include "mpcb_plant.h"
 
 #ifndef MPCB_WAVES_PER_SIMD
 #define MPCB_WAVES_PER_SIMD 1
@@ -170,240 +171,58 @@ __global__ __launch_bounds__(64) void mpcb_eval(const MpcbEvalArgs a) {
   ::mpcb_eval<NX, PARAMS>(a, (int)blockIdx.x, mpcb_lds);
 }
 
-// f(x,u) of the configured model: the reference's `mpc_solver.f` (kin.py:153-159, dyn.py:156-177); host and device
-__host__ __device__ inline void model_rhs(const mpcb_config& c, const double* x, const double* u, double* xdot) {
-#pragma clang fp contract(off)   // every product and sum rounded on its own, as numpy / CasADi evaluate the reference's expressions
-  if (c.model == MPCB_MODEL_KIN) {                       // kin.py:153-156
-    xdot[0] = x[3] * cos(x[2]);
-    xdot[1] = x[3] * sin(x[2]);
-    xdot[2] = x[3] * tan(u[0]) / c.veh_l;
-    xdot[3] = u[1];
-  } else {                                               // dyn.py:156-170
-    const double phi = x[2], vx = x[3], vy = x[4], r = x[5], df = u[0], ax = u[1];
-    const double af = df - (vy + c.veh_lf * r) / vx, ar = -(vy - c.veh_lr * r) / vx;
-    const double Cf = c.Fymax_f * 2 * c.aopt_f / (c.aopt_f * c.aopt_f + af * af);
-    const double Cr = c.Fymax_r * 2 * c.aopt_r / (c.aopt_r * c.aopt_r + ar * ar);
-    const double Fcf = -Cf * af, Fcr = -Cr * ar;
-    xdot[0] = vx * cos(phi) - vy * sin(phi);
-    xdot[1] = vx * sin(phi) + vy * cos(phi);
-    xdot[2] = r;
-    xdot[3] = ax + r * vy;
-    xdot[4] = -r * vx + 2.0 / c.veh_m * (Fcf * cos(df) + Fcr);
-    xdot[5] = 2.0 / c.veh_Iz * (c.veh_lf * Fcf - c.veh_lr * Fcr);
-  }
-}
+// ---- the closed loop between two solves: index arithmetic around the per-instance pieces of mpcb_plant.h ---------------------------------
+// One thread per instance (tiny, HBM-bound, runs between two solves of the closed loop).
+//   c0 / cfgs: the handle's config, and the [B] per-instance configs of a parameter set or NULL.  Instance b is advanced with the
+//         wheelbase and the vehicle / tyre constants of cfgs[b]; N, n_obs and the integrator are structural, the same in every row.
+//   move_obs: 0 none, 1 every obstacle one constant-velocity step, 2 only the first one
+//   hold: 1 = an instance whose solve ended neither solved nor acceptable applies its previous plan instead (hold-and-shift)
+//   T: length of the executed step (cfg.T, or T_0 of the time grid)
 
-// closed-loop helper: plant step with the first control, warm-start shift, obstacle advance; either model.
-// one thread per instance (tiny, HBM-bound, runs between two solves of the closed loop)
-//   main_cbf_kin_c_sim.py:16-26 / main_cbf_dyn_c_sim.py:15-25 (shift_movement), main_cbf_kin_c_sim_pre.py:106 (obstacle advance)
-// NX is a template parameter so that x[] / f[] live in registers (with a run-time nx the compiler parked them in LDS).
-//   move_obs: 0 none, 1 every obstacle one constant-velocity step, 2 only the first one (what main_cbf_kin_c_sim_pre.py:106 does)
-//   hold: 1 = an instance whose solve did not end with MPCB_ST_SOLVED applies its previous plan instead (the shifted warm start
-//         z0 IS that plan, already moved one step): hold-and-shift, prior art `reference code/MPC-D-CBF.py:341-353`
+// mpcb_closed_loop*: both halves of the step in one launch, and the histories.  status: column `step` of the [B, st_stride] history.
 template <int NX>
-__global__ __launch_bounds__(128) void mpcb_advance(const mpcb_config c, int B, int nz, const double* __restrict__ z,
-                                                    double* __restrict__ x0, double* __restrict__ z0, double* __restrict__ obs,
-                                                    double* __restrict__ x_hist, double* __restrict__ u_hist,
+__global__ __launch_bounds__(128) void mpcb_advance(const mpcb_config c0, const mpcb_config* __restrict__ cfgs, int B, int nz,
+                                                    const double* __restrict__ z, double* __restrict__ x0, double* __restrict__ z0,
+                                                    double* __restrict__ obs, double* __restrict__ x_hist, double* __restrict__ u_hist,
                                                     const int32_t* __restrict__ status, int st_stride, int step, int steps,
                                                     int move_obs, int hold, double T) {
-#pragma clang fp contract(off)   // st = x0 + T*f and x += v*cos(theta)*dt with numpy's roundings (no FMA): bit-equal to the reference's helpers
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const int N = c.N, n_obs = c.n_obs;     // T: length of the executed step (cfg.T, or T_0 of the time grid)
-  double* w = z0 + (size_t)b * nz;
-  // the plan that is executed: this step's solution, or (hold) the previous plan kept in z0
-  const int st_b = status ? status[(size_t)b * st_stride] : MPCB_ST_SOLVED;
-  const bool keep = hold && st_b != MPCB_ST_SOLVED && st_b != MPCB_ST_ACCEPTABLE;
-  const double* zb = keep ? w : z + (size_t)b * nz;
+  const mpcb_config& c = cfgs ? cfgs[b] : c0;
   double* xb = x0 + (size_t)b * NX;
-  const double u[2] = {zb[0], zb[1]};
-  double x[MPCB_NX_MAX] = {0, 0, 0, 0, 0, 0}, f[MPCB_NX_MAX];   // constant indices after unrolling: registers
-#pragma unroll
-  for (int q = 0; q < NX; ++q) x[q] = xb[q];
-  model_rhs(c, x, u, f);
-  if (c.integrator == MPCB_INT_RK4) {                                             // the plant follows the NLP's integrator: classical RK4 step, control held
-    double k2[MPCB_NX_MAX], k3[MPCB_NX_MAX], k4[MPCB_NX_MAX], xt[MPCB_NX_MAX] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int q = 0; q < NX; ++q) xt[q] = x[q] + 0.5 * T * f[q];
-    model_rhs(c, xt, u, k2);
-#pragma unroll
-    for (int q = 0; q < NX; ++q) xt[q] = x[q] + 0.5 * T * k2[q];
-    model_rhs(c, xt, u, k3);
-#pragma unroll
-    for (int q = 0; q < NX; ++q) xt[q] = x[q] + T * k3[q];
-    model_rhs(c, xt, u, k4);
-#pragma unroll
-    for (int q = 0; q < NX; ++q) f[q] = (f[q] + 2.0 * k2[q] + 2.0 * k3[q] + k4[q]) / 6.0;
-  }
-#pragma unroll
-  for (int q = 0; q < NX; ++q) xb[q] = x[q] + T * f[q];                          // st = x0 + T f(x0, u[0])  (RK4: T times the weighted slope)
+  double u[2];
+  mpcbp::commit<NX>(c0.N, hold, status[(size_t)b * st_stride], z + (size_t)b * nz, z0 + (size_t)b * nz, u);
+  mpcbp::plant<NX>(c, T, u, move_obs, xb, obs + (size_t)b * c0.n_obs * 6);
   if (u_hist) { u_hist[((size_t)b * steps + step) * 2] = u[0]; u_hist[((size_t)b * steps + step) * 2 + 1] = u[1]; }
   if (x_hist) {
     double* h = x_hist + ((size_t)b * (steps + 1) + step + 1) * NX;
 #pragma unroll
     for (int q = 0; q < NX; ++q) h[q] = xb[q];
-  }
-  // u <- [u[1:]; u[-1]],  x_f <- [x_f[1:]; x_f[-1]]   (in place when zb == w: ascending order reads ahead of the writes)
-  for (int i = 0; i < N; ++i) { int s = (i + 1 < N) ? i + 1 : N - 1; const double a0 = zb[2 * s], a1 = zb[2 * s + 1]; w[2 * i] = a0; w[2 * i + 1] = a1; }
-  for (int i = 0; i <= N; ++i) {
-    int s = (i + 1 <= N) ? i + 1 : N;
-    double t[NX];
-#pragma unroll
-    for (int q = 0; q < NX; ++q) t[q] = zb[2 * N + NX * s + q];
-#pragma unroll
-    for (int q = 0; q < NX; ++q) w[2 * N + NX * i + q] = t[q];
-  }
-  // obstacles move one step with constant velocity and heading (Obs_prediction.py:27-30)
-  const int nmove = move_obs == 1 ? n_obs : move_obs == 2 ? (n_obs < 1 ? n_obs : 1) : 0;
-  for (int j = 0; j < nmove; ++j) {
-    double* o = obs + ((size_t)b * n_obs + j) * 6;
-    o[0] += o[3] * cos(o[2]) * T; o[1] += o[3] * sin(o[2]) * T;
-  }
-}
-
-// mpcb_advance of the closed loop with per-instance problem data (mpcb_closed_loop_params): the plant step of instance b uses the wheelbase
-// and the vehicle / tyre constants of row b of the parameter set.  Euler only (the parameter sets exclude RK4); N, n_obs and T are
-// structural, so the shift and the obstacle advance are those of mpcb_advance.  The same expressions in the same order as mpcb_advance:
-// a mixed closed loop is bit-equal to the loops of the plain handles on their instances.
-template <int NX>
-__global__ __launch_bounds__(128) void mpcb_advance_params(const mpcb_config* __restrict__ cfgs, int B, int nz, const double* __restrict__ z,
-                                                           double* __restrict__ x0, double* __restrict__ z0, double* __restrict__ obs,
-                                                           double* __restrict__ x_hist, double* __restrict__ u_hist,
-                                                           const int32_t* __restrict__ status, int st_stride, int step, int steps,
-                                                           int move_obs, int hold, double T) {
-#pragma clang fp contract(off)
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const mpcb_config& c = cfgs[b];
-  const int N = c.N, n_obs = c.n_obs;
-  double* w = z0 + (size_t)b * nz;
-  const int st_b = status ? status[(size_t)b * st_stride] : MPCB_ST_SOLVED;
-  const bool keep = hold && st_b != MPCB_ST_SOLVED && st_b != MPCB_ST_ACCEPTABLE;
-  const double* zb = keep ? w : z + (size_t)b * nz;
-  double* xb = x0 + (size_t)b * NX;
-  const double u[2] = {zb[0], zb[1]};
-  double x[MPCB_NX_MAX] = {0, 0, 0, 0, 0, 0}, f[MPCB_NX_MAX];
-#pragma unroll
-  for (int q = 0; q < NX; ++q) x[q] = xb[q];
-  model_rhs(c, x, u, f);
-#pragma unroll
-  for (int q = 0; q < NX; ++q) xb[q] = x[q] + T * f[q];
-  if (u_hist) { u_hist[((size_t)b * steps + step) * 2] = u[0]; u_hist[((size_t)b * steps + step) * 2 + 1] = u[1]; }
-  if (x_hist) {
-    double* h = x_hist + ((size_t)b * (steps + 1) + step + 1) * NX;
-#pragma unroll
-    for (int q = 0; q < NX; ++q) h[q] = xb[q];
-  }
-  for (int i = 0; i < N; ++i) { int s = (i + 1 < N) ? i + 1 : N - 1; const double a0 = zb[2 * s], a1 = zb[2 * s + 1]; w[2 * i] = a0; w[2 * i + 1] = a1; }
-  for (int i = 0; i <= N; ++i) {
-    int s = (i + 1 <= N) ? i + 1 : N;
-    double t[NX];
-#pragma unroll
-    for (int q = 0; q < NX; ++q) t[q] = zb[2 * N + NX * s + q];
-#pragma unroll
-    for (int q = 0; q < NX; ++q) w[2 * N + NX * i + q] = t[q];
-  }
-  const int nmove = move_obs == 1 ? n_obs : move_obs == 2 ? (n_obs < 1 ? n_obs : 1) : 0;
-  for (int j = 0; j < nmove; ++j) {
-    double* o = obs + ((size_t)b * n_obs + j) * 6;
-    o[0] += o[3] * cos(o[2]) * T; o[1] += o[3] * sin(o[2]) * T;
   }
 }
 
 // ---- the stepwise loop (mpcb_loop_*): mpcb_advance cut at the seam between controller and plant ---------------------------------------
-// mpcb_loop_commit is the controller's half: which plan is executed (hold-and-shift), its first control to u0, the plan shifted one stage
-// into the warm start w, the counters.  mpcb_loop_plant is the plant's half: x0 <- x0 + T f(x0, u0) and the obstacle move.  Both repeat
-// mpcb_advance's expressions in its order, so that (commit, plant) after a solve leaves exactly what mpcb_advance leaves.
-// one thread per instance
+// mpcb_loop_commit is the controller's half (the executed plan's first control to u0, the plan shifted into the warm start w0, the
+// counters), mpcb_loop_plant the plant's half: (commit, plant) after a solve leaves exactly what mpcb_advance leaves.
 template <int NX>
 __global__ __launch_bounds__(128) void mpcb_loop_commit(int B, int N, int nz, const double* __restrict__ z, double* __restrict__ w0,
                                                         double* __restrict__ u0, const int32_t* __restrict__ status, int hold,
                                                         int32_t* __restrict__ n_steps, int32_t* __restrict__ n_failed) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  double* w = w0 + (size_t)b * nz;
-  const int st_b = status[b];
-  const bool failed = st_b != MPCB_ST_SOLVED && st_b != MPCB_ST_ACCEPTABLE;
-  const bool keep = hold && failed;
-  const double* zb = keep ? w : z + (size_t)b * nz;
-  u0[(size_t)b * 2] = zb[0]; u0[(size_t)b * 2 + 1] = zb[1];
-  // u <- [u[1:]; u[-1]],  x_f <- [x_f[1:]; x_f[-1]]   (in place when zb == w: ascending order reads ahead of the writes)
-  for (int i = 0; i < N; ++i) { int s = (i + 1 < N) ? i + 1 : N - 1; const double a0 = zb[2 * s], a1 = zb[2 * s + 1]; w[2 * i] = a0; w[2 * i + 1] = a1; }
-  for (int i = 0; i <= N; ++i) {
-    int s = (i + 1 <= N) ? i + 1 : N;
-    double t[NX];
-#pragma unroll
-    for (int q = 0; q < NX; ++q) t[q] = zb[2 * N + NX * s + q];
-#pragma unroll
-    for (int q = 0; q < NX; ++q) w[2 * N + NX * i + q] = t[q];
-  }
+  double u[2];
+  const bool failed = mpcbp::commit<NX>(N, hold, status[b], z + (size_t)b * nz, w0 + (size_t)b * nz, u);
+  u0[(size_t)b * 2] = u[0]; u0[(size_t)b * 2 + 1] = u[1];
   n_steps[b] += 1;
   if (failed) n_failed[b] += 1;
 }
 
-// model_rhs with the model fixed at compile time by NX (4: kinematic, 6: dynamic): the expressions of model_rhs, copied, in its order.
-// A copy and not a call: with the model a run-time branch the compiler indexes xdot[] dynamically and parks it in scratch (mpcb_advance
-// does), and a further caller of model_rhs moves the instruction text of the existing kernels.
-template <int NX>
-__device__ __forceinline__ void mpcb_loop_rhs(const mpcb_config& c, const double* x, const double* u, double* xdot) {
-#pragma clang fp contract(off)
-  if constexpr (NX == 4) {
-    xdot[0] = x[3] * cos(x[2]);
-    xdot[1] = x[3] * sin(x[2]);
-    xdot[2] = x[3] * tan(u[0]) / c.veh_l;
-    xdot[3] = u[1];
-  } else {
-    const double phi = x[2], vx = x[3], vy = x[4], r = x[5], df = u[0], ax = u[1];
-    const double af = df - (vy + c.veh_lf * r) / vx, ar = -(vy - c.veh_lr * r) / vx;
-    const double Cf = c.Fymax_f * 2 * c.aopt_f / (c.aopt_f * c.aopt_f + af * af);
-    const double Cr = c.Fymax_r * 2 * c.aopt_r / (c.aopt_r * c.aopt_r + ar * ar);
-    const double Fcf = -Cf * af, Fcr = -Cr * ar;
-    xdot[0] = vx * cos(phi) - vy * sin(phi);
-    xdot[1] = vx * sin(phi) + vy * cos(phi);
-    xdot[2] = r;
-    xdot[3] = ax + r * vy;
-    xdot[4] = -r * vx + 2.0 / c.veh_m * (Fcf * cos(df) + Fcr);
-    xdot[5] = 2.0 / c.veh_Iz * (c.veh_lf * Fcf - c.veh_lr * Fcr);
-  }
-}
-
-// cfgs: [B] per-instance configs (the loop was created with a parameter set: constants of row b, as in mpcb_advance_params), or NULL
-//   move_obs: 0 none, 1 every obstacle one constant-velocity step, 2 only the first one
 template <int NX>
 __global__ __launch_bounds__(128) void mpcb_loop_plant(const mpcb_config c0, const mpcb_config* __restrict__ cfgs, int B, double* __restrict__ x0,
                                                        const double* __restrict__ u0, double* __restrict__ obs, int move_obs, double T) {
-#pragma clang fp contract(off)   // as mpcb_advance: every product and sum rounded on its own
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const mpcb_config& c = cfgs ? cfgs[b] : c0;
-  const int n_obs = c0.n_obs;             // structural: the same in every row
-  double* xb = x0 + (size_t)b * NX;
-  const double u[2] = {u0[(size_t)b * 2], u0[(size_t)b * 2 + 1]};
-  double x[NX], f[NX];
-#pragma unroll
-  for (int q = 0; q < NX; ++q) x[q] = xb[q];
-  mpcb_loop_rhs<NX>(c, x, u, f);
-  if (c0.integrator == MPCB_INT_RK4) {
-    double k2[NX], k3[NX], k4[NX], xt[NX];
-#pragma unroll
-    for (int q = 0; q < NX; ++q) xt[q] = x[q] + 0.5 * T * f[q];
-    mpcb_loop_rhs<NX>(c, xt, u, k2);
-#pragma unroll
-    for (int q = 0; q < NX; ++q) xt[q] = x[q] + 0.5 * T * k2[q];
-    mpcb_loop_rhs<NX>(c, xt, u, k3);
-#pragma unroll
-    for (int q = 0; q < NX; ++q) xt[q] = x[q] + T * k3[q];
-    mpcb_loop_rhs<NX>(c, xt, u, k4);
-#pragma unroll
-    for (int q = 0; q < NX; ++q) f[q] = (f[q] + 2.0 * k2[q] + 2.0 * k3[q] + k4[q]) / 6.0;
-  }
-#pragma unroll
-  for (int q = 0; q < NX; ++q) xb[q] = x[q] + T * f[q];
-  const int nmove = move_obs == 1 ? n_obs : move_obs == 2 ? (n_obs < 1 ? n_obs : 1) : 0;
-  for (int j = 0; j < nmove; ++j) {
-    double* o = obs + ((size_t)b * n_obs + j) * 6;
-    o[0] += o[3] * cos(o[2]) * T; o[1] += o[3] * sin(o[2]) * T;
-  }
+  mpcbp::plant<NX>(cfgs ? cfgs[b] : c0, T, u0 + (size_t)b * 2, move_obs, x0 + (size_t)b * NX, obs + (size_t)b * c0.n_obs * 6);
 }
 
 // mpcb_loop_reset with a mask: the warm start and the counters of the masked instances back to zero
@@ -862,16 +681,6 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   return MPCB_OK;
 }
 
-void launch_advance_params(int nx, hipStream_t s, const mpcb_config* d_cfgs, int B, int nz, const double* z, double* x0, double* z0, double* obs,
-                           double* x_hist, double* u_hist, const int32_t* status, int st_stride, int step, int steps, int move_obs, int hold, double T) {
-  if (nx == 6)
-    hipLaunchKernelGGL(mpcb_advance_params<6>, dim3((B + 127) / 128), dim3(128), 0, s, d_cfgs, B, nz, z, x0, z0, obs, x_hist, u_hist, status, st_stride,
-                       step, steps, move_obs, hold, T);
-  else
-    hipLaunchKernelGGL(mpcb_advance_params<4>, dim3((B + 127) / 128), dim3(128), 0, s, d_cfgs, B, nz, z, x0, z0, obs, x_hist, u_hist, status, st_stride,
-                       step, steps, move_obs, hold, T);
-}
-
 // what the tracking entry points support: the kinematic model on a single-device handle
 int check_track(mpcb_handle* h) {
   mpcbd::Variant v;
@@ -1100,16 +909,6 @@ int lane_done(mpcb_handle* h, int lane) {
   return MPCB_OK;
 }
 
-// (named before closed_loop_impl names mpcb_advance: kernels are emitted in the order of their first use, and mpcb_advance<4> stays the
-// last function of the code object, where the resource table of tools/kernel_resources.py counts no trailing padding for it)
-void launch_loop_plant(int nx, hipStream_t s, const mpcb_config& cfg, const mpcb_config* d_cfgs, int B, double* x0, const double* u0, double* obs,
-                       int move_obs, double T) {
-  if (nx == 6)
-    hipLaunchKernelGGL(mpcb_loop_plant<6>, dim3((B + 127) / 128), dim3(128), 0, s, cfg, d_cfgs, B, x0, u0, obs, move_obs, T);
-  else
-    hipLaunchKernelGGL(mpcb_loop_plant<4>, dim3((B + 127) / 128), dim3(128), 0, s, cfg, d_cfgs, B, x0, u0, obs, move_obs, T);
-}
-
 // One controller step with everything on the device, queued on lane `lane`: [predict ->] solve from the loop's warm start -> commit.
 // Every refusal comes before the first launch, so a refused step leaves the loop as it was.
 int loop_step_on_device(mpcb_handle* h, mpcb_loop* L, const double* x0, const double* xs, const double* x_ref, const double* obs, int32_t obs_kind,
@@ -1133,10 +932,10 @@ int loop_step_on_device(mpcb_handle* h, mpcb_loop* L, const double* x0, const do
   }
   { int rc = solve_on_device(h, sv, lane); if (rc != MPCB_OK) return rc; }
   const int hold = (L->flags & MPCB_CL_HOLD_ON_FAILURE) ? 1 : 0;
-  if (h->nx == 6)
-    hipLaunchKernelGGL(mpcb_loop_commit<6>, dim3((B + 127) / 128), dim3(128), 0, s, B, N, nz, sv.z, L->d_w, u0, sv.status, hold, L->d_cnt, L->d_cnt + B);
-  else
-    hipLaunchKernelGGL(mpcb_loop_commit<4>, dim3((B + 127) / 128), dim3(128), 0, s, B, N, nz, sv.z, L->d_w, u0, sv.status, hold, L->d_cnt, L->d_cnt + B);
+  mpcbp::visit_nx(h->nx, [&](auto nx) {
+    hipLaunchKernelGGL(mpcb_loop_commit<decltype(nx)::value>, dim3((B + 127) / 128), dim3(128), 0, s, B, N, nz, sv.z, L->d_w, u0, sv.status, hold,
+                       L->d_cnt, L->d_cnt + B);
+  });
   HIP_TRY(h, hipGetLastError());
   return lane_done(h, lane);            // the lane's `done` now marks the end of the commit, not of the solve
 }
@@ -1642,14 +1441,10 @@ static int closed_loop_impl(mpcb_handle* h, int32_t B, int32_t steps, const doub
     sv.st_stride = steps; sv.xref = d_xr; sv.cfgs = d_cfgs;
     int rc = solve_on_device(h, sv);
     if (rc != MPCB_OK) return rc;
-    if (d_cfgs)            // solve and plant step both from row b of the parameter set
-      launch_advance_params(nx, s, d_cfgs, B, nz, d_z, d_x0, d_z0, d_obs, d_xh, d_uh, d_st + t, steps, t, steps, move, hold, Tstep);
-    else if (nx == 6)
-      hipLaunchKernelGGL(mpcb_advance<6>, dim3((B + 127) / 128), dim3(128), 0, s, h->cfg, B, nz, d_z, d_x0, d_z0, d_obs, d_xh, d_uh,
-                         d_st + t, steps, t, steps, move, hold, Tstep);
-    else
-      hipLaunchKernelGGL(mpcb_advance<4>, dim3((B + 127) / 128), dim3(128), 0, s, h->cfg, B, nz, d_z, d_x0, d_z0, d_obs, d_xh, d_uh,
-                         d_st + t, steps, t, steps, move, hold, Tstep);
+    mpcbp::visit_nx(nx, [&](auto nxc) {      // solve and plant step both from row b of the parameter set, where there is one
+      hipLaunchKernelGGL(mpcb_advance<decltype(nxc)::value>, dim3((B + 127) / 128), dim3(128), 0, s, h->cfg, d_cfgs, B, nz, d_z, d_x0, d_z0, d_obs,
+                         d_xh, d_uh, d_st + t, steps, t, steps, move, hold, Tstep);
+    });
     HIP_TRY(h, hipGetLastError());
   }
   if (x_hist) HIP_TRY(h, hipMemcpyAsync(x_hist, d_xh, (size_t)B * (steps + 1) * nx * 8, hipMemcpyDeviceToHost, s));
@@ -1969,7 +1764,9 @@ int mpcb_loop_advance_device(mpcb_handle* h, mpcb_loop* L, double* d_x0, const d
   const int move = (!d_obs || h->cfg.n_obs == 0) ? 0 : (flags & MPCB_CL_ADVANCE_FIRST_ONLY) ? 2 : 1;
   const double Tstep = h->d_tgrid ? h->T0 : h->cfg.T;
   const mpcb_config* d_cfgs = L->params ? L->params->d_cfgs : nullptr;
-  launch_loop_plant(h->nx, s, h->cfg, d_cfgs, B, d_x0, d_u0, d_obs, move, Tstep);
+  mpcbp::visit_nx(h->nx, [&](auto nx) {
+    hipLaunchKernelGGL(mpcb_loop_plant<decltype(nx)::value>, dim3((B + 127) / 128), dim3(128), 0, s, h->cfg, d_cfgs, B, d_x0, d_u0, d_obs, move, Tstep);
+  });
   HIP_TRY(h, hipGetLastError());
   { int rc = lane_done(h, lane); if (rc != MPCB_OK) return rc; }
   return sync ? mpcb_sync(h) : MPCB_OK;
@@ -2221,7 +2018,7 @@ int mpcb_timing(mpcb_handle* h, int32_t reset, int32_t* launches, double* total_
 int mpcb_model_rhs(const mpcb_config* c, const double* x, const double* u, double* xdot) {
   if (!c || !x || !u || !xdot) return MPCB_E_INVALID;
   if (c->model != MPCB_MODEL_KIN && c->model != MPCB_MODEL_DYN) return MPCB_E_INVALID;
-  model_rhs(*c, x, u, xdot);
+  mpcbp::visit_nx(c->model == MPCB_MODEL_DYN ? 6 : 4, [&](auto nx) { mpcbp::model_rhs<decltype(nx)::value>(*c, x, u, xdot); });
   return MPCB_OK;
 }
 

@@ -20,6 +20,17 @@ def lib():
     return _LIB
 
 
+def _rows(cfgs):
+    """A ctypes array of MpcbConfig from a sequence of configs (an array, e.g. from solver.vary, and None pass through)."""
+    if cfgs is None or (isinstance(cfgs, C.Array) and cfgs._type_ is MpcbConfig):
+        return cfgs
+    rows = list(cfgs)
+    arr = (MpcbConfig * len(rows))()
+    for b, r in enumerate(rows):
+        C.memmove(C.byref(arr[b]), C.byref(r), C.sizeof(MpcbConfig))
+    return arr
+
+
 def solve(cfg, x0, xs, obs=None, z0=None, trace_instance=-1, tgrid=None, x_ref=None, cfgs=None):
     """The solve stepped on the CPU -> dict(z, obj, status, iters, kkt, lam_g, lam_x; trace with trace_instance >= 0).  x_ref [B, N, 4]: the tracking solve.
     cfgs: instance b stepped under cfgs[b] (a ctypes array of MpcbConfig, e.g. from solver.vary, or a sequence of configs); cfg then
@@ -41,11 +52,7 @@ def solve(cfg, x0, xs, obs=None, z0=None, trace_instance=-1, tgrid=None, x_ref=N
         z0 = np.ascontiguousarray(z0, dtype=np.float64).reshape(B, nz)
     if x_ref is not None:
         x_ref = np.ascontiguousarray(np.asarray(x_ref, dtype=np.float64).reshape(B, N, 4))
-    if cfgs is not None and not (isinstance(cfgs, C.Array) and cfgs._type_ is MpcbConfig):
-        rows = list(cfgs)
-        cfgs = (MpcbConfig * len(rows))()
-        for b, r in enumerate(rows):
-            C.memmove(C.byref(cfgs[b]), C.byref(r), C.sizeof(MpcbConfig))
+    cfgs = _rows(cfgs)
     assert cfgs is None or len(cfgs) == B, "one config per instance"
     z = np.zeros((B, nz)); obj = np.zeros(B); st = np.zeros(B, np.int32); it = np.zeros(B, np.int32)
     kkt = np.zeros((B, 4)); lam_g = np.zeros((B, ng)); lam_x = np.zeros((B, nz))
@@ -85,3 +92,32 @@ def dyn_model(cfg, X, U, lam):
     F = np.zeros(6); jac = np.zeros(16); hess = np.zeros(13)
     lib().mpcb_emu_dyn_model(C.byref(cfg), dptr(X), dptr(U), dptr(lam), dptr(F), dptr(jac), dptr(hess))
     return F, jac, hess
+
+
+def advance(cfg, z, x0, w, status, step=0, obs=None, move_obs=0, hold=False, T=None, cfgs=None, x_hist=None, u_hist=None, counters=None):
+    """One step of the closed loop between two solves on the host (csrc/mpcb_plant.h composed as the kernel mpcb_advance composes it,
+    plus mpcb_loop_commit's u0 and counters).  z [B,nz] this step's solutions, or None: the plan is the warm start itself, shifted in
+    place; w [B,nz] the warm start; status [B,steps], column `step` is read; x_hist [B,steps+1,nx] / u_hist [B,steps,2] or None;
+    counters (n_steps [B], n_failed [B]) or None.  Nothing given is changed: returns dict(x0, w, obs, u0, x_hist, u_hist, n_steps,
+    n_failed) with copies."""
+    c64 = lambda a: None if a is None else np.array(a, dtype=np.float64, order="C")   # noqa: E731 (a copy)
+    x0, w, obs, x_hist, u_hist = c64(x0), c64(w), c64(obs), c64(x_hist), c64(u_hist)
+    z = w if z is None else np.ascontiguousarray(z, dtype=np.float64)
+    status = np.ascontiguousarray(np.asarray(status, dtype=np.int32).reshape(len(x0), -1))
+    B, steps = status.shape
+    assert x0.shape == (B, cfg.nx()) and w.shape == z.shape == (B, cfg.nz()) and 0 <= step < steps
+    assert obs is None or obs.shape == (B, cfg.n_obs, 6)
+    assert obs is not None or move_obs == 0 or cfg.n_obs == 0
+    assert x_hist is None or x_hist.shape == (B, steps + 1, cfg.nx())
+    assert u_hist is None or u_hist.shape == (B, steps, 2)
+    cfgs = _rows(cfgs)
+    assert cfgs is None or len(cfgs) == B, "one config per instance"
+    n_steps, n_failed = (None, None) if counters is None else (np.array(a, dtype=np.int32) for a in counters)
+    u0 = np.zeros((B, 2))
+    f = lib().mpcb_emu_advance; f.restype = C.c_int
+    rc = f(C.byref(cfg), cfgs, C.c_int32(B), dptr(z), dptr(x0), dptr(w), dptr(obs), dptr(x_hist), dptr(u_hist), iptr(status), C.c_int32(step),
+           C.c_int32(steps), C.c_int32(move_obs), C.c_int32(1 if hold else 0), C.c_double(cfg.T if T is None else T), dptr(u0),
+           iptr(n_steps), iptr(n_failed))
+    if rc != 0:
+        raise RuntimeError("mpcb_emu_advance failed with code %d" % rc)
+    return dict(x0=x0, w=w, obs=obs, u0=u0, x_hist=x_hist, u_hist=u_hist, n_steps=n_steps, n_failed=n_failed)

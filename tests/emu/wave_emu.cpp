@@ -9,6 +9,7 @@
 #define MPCB_WAVE_EMU 1
 #include "../../mpc_motion_planning_amd/csrc/mpcb_kernel_dyn.h"
 #include "../../mpc_motion_planning_amd/csrc/mpcb_dispatch.h"
+#include "../../mpc_motion_planning_amd/csrc/mpcb_plant.h"
 
 #include <thread>
 #include <limits>
@@ -143,4 +144,30 @@ extern "C" int mpcb_emu_dyn_model(const mpcb_config* cfg, const double* X, const
   const double h[13] = {H.h22, H.h23, H.h24, H.h33, H.h34, H.h35, H.h44, H.h45, H.h55, H.h38, H.h48, H.h58, H.h88};
   for (int i = 0; i < 13; ++i) hess13[i] = h[i];
   return 0;
+}
+
+// One step of the closed loop between two solves on the host: the per-instance pieces of mpcb_plant.h composed as the kernel mpcb_advance
+// composes them (its arguments, status being column `step` of the [B, steps] history), plus what mpcb_loop_commit adds: the executed
+// control to u0 [B,2] and the counters.  x_hist, u_hist, u0 and the counters may be NULL; obs may be NULL when nothing moves.
+extern "C" int mpcb_emu_advance(const mpcb_config* cfg, const mpcb_config* cfgs, int32_t B, const double* z, double* x0, double* z0, double* obs,
+                                double* x_hist, double* u_hist, const int32_t* status, int32_t step, int32_t steps, int32_t move_obs,
+                                int32_t hold, double T, double* u0, int32_t* n_steps, int32_t* n_failed) {
+  if (!cfg || !z || !x0 || !z0 || !status) return MPCB_E_INVALID;
+  return mpcbp::visit_nx(cfg->model == MPCB_MODEL_DYN ? 6 : 4, [&](auto nx) {
+    constexpr int NX = decltype(nx)::value;
+    const int nz = 2 * cfg->N + NX * (cfg->N + 1);
+    for (int b = 0; b < B; ++b) {
+      const mpcb_config& c = cfgs ? cfgs[b] : *cfg;
+      double* xb = x0 + (size_t)b * NX;
+      double u[2];
+      const bool failed = mpcbp::commit<NX>(cfg->N, hold, status[(size_t)b * steps + step], z + (size_t)b * nz, z0 + (size_t)b * nz, u);
+      mpcbp::plant<NX>(c, T, u, move_obs, xb, obs + (size_t)b * cfg->n_obs * 6);
+      if (u_hist) { u_hist[((size_t)b * steps + step) * 2] = u[0]; u_hist[((size_t)b * steps + step) * 2 + 1] = u[1]; }
+      if (x_hist) for (int q = 0; q < NX; ++q) x_hist[((size_t)b * (steps + 1) + step + 1) * NX + q] = xb[q];
+      if (u0) { u0[(size_t)b * 2] = u[0]; u0[(size_t)b * 2 + 1] = u[1]; }
+      if (n_steps) n_steps[b] += 1;
+      if (n_failed && failed) n_failed[b] += 1;
+    }
+    return (int)MPCB_OK;
+  });
 }

@@ -18,6 +18,7 @@ import collections
 import numpy as np
 
 from mpc_motion_planning_amd import scenes as _scenes, _abi
+from tests import config_cases as cc
 
 N, T = 30, 0.1
 NOISE_SD = np.array([0.05, 0.02, 0.002, 0.05])          # m, m, rad, m/s: added to the state after every plant step
@@ -155,6 +156,119 @@ def teacher_forced(scn, cfg, oracle, log, hold):
         plans.append(plan)
         w = shift_plan(plan)
     return ({k: np.concatenate(v) for k, v in ctl.items()}, {k: np.concatenate(v) for k, v in ref.items()}, plans)
+
+
+# ---- the library's plant step on its own: the cases of tests/golden/plant_step.npz ------------------------------------------------------
+# ControlLoop.advance_device twice in a row (the second step starts from lateral speed and yaw rate that are not zero), recorded on the
+# MI355X by tests/golden/make_plant_fixture.py from the build before csrc/mpcb_plant.h existed.  tests/test_loop_gpu.py asserts those
+# bytes, tests/test_loop_cpu.py puts the CPU twin and the numpy statement below within 1e-10 of them.
+PLANT_B, PLANT_SEED, PLANT_STEPS = 64, 29, 2
+TIME_GRID = (0.08,) * 10 + (0.12,) * 20                  # T_0 = 0.08 is the plant's step, not cfg.T
+
+# rows: the two cases of tests/config_cases.py whose configs alternate over the instances (a parameter set), or None
+# move: 0 no obstacle moves, 1 every obstacle, 2 the first one only
+PlantCase = collections.namedtuple("PlantCase", "name model N n_obs integrator tgrid rows move")
+PLANT_CASES = [
+    PlantCase("kin_euler", _abi.MODEL_KIN, 30, 1, _abi.INT_EULER, None, None, 1),
+    PlantCase("kin_rk4", _abi.MODEL_KIN, 30, 1, _abi.INT_RK4, None, None, 1),
+    PlantCase("dyn_euler", _abi.MODEL_DYN, 20, 1, _abi.INT_EULER, None, None, 1),
+    PlantCase("time_grid", _abi.MODEL_KIN, 30, 1, _abi.INT_EULER, TIME_GRID, None, 1),
+    PlantCase("rows_kin", _abi.MODEL_KIN, 30, 1, _abi.INT_EULER, None, ("default", "geometry"), 1),
+    PlantCase("rows_dyn", _abi.MODEL_DYN, 20, 1, _abi.INT_EULER, None, ("dyn_default", "dyn_vehicle"), 1),
+    PlantCase("obs3_all", _abi.MODEL_KIN, 30, 3, _abi.INT_EULER, None, None, 1),
+    PlantCase("obs3_first", _abi.MODEL_KIN, 30, 3, _abi.INT_EULER, None, None, 2),
+    PlantCase("obs3_none", _abi.MODEL_KIN, 30, 3, _abi.INT_EULER, None, None, 0),
+]
+
+
+def plant_inputs_key(case):
+    """The cases of one model and obstacle count share their inputs."""
+    return "%s%d" % ("dyn" if case.model == _abi.MODEL_DYN else "kin", case.n_obs)
+
+
+def plant_configs(case, default_config):
+    """(cfg, rows): the config of the handle and, for a parameter-set case, the config of every instance."""
+    cfg = default_config(model=case.model, N=case.N, T=T, n_obs=case.n_obs)
+    cfg.integrator = case.integrator
+    if case.rows is None:
+        return cfg, None
+    two = [cc.base(cc.BY_NAME[n], default_config) for n in case.rows]
+    return two[0], [two[b % 2] for b in range(PLANT_B)]
+
+
+def plant_inputs(case, cfg):
+    """(x0 [B,nx], u0 [B,2], obs [B,n_obs,6]): states of sample_c2 / sample_c4, controls uniform in the config's box, obstacles with
+    headings and speeds that make both of cos and sin matter."""
+    rng = np.random.default_rng(PLANT_SEED)
+    if case.model == _abi.MODEL_DYN:
+        x0, _, obs = _scenes.sample_c4(PLANT_B, seed=PLANT_SEED, n_obs=case.n_obs)
+    else:
+        x0 = _scenes.sample_c2(PLANT_B, seed=PLANT_SEED)[0]
+        obs = _scenes.sample_c3(PLANT_B, N=case.N, dt=T, seed=PLANT_SEED, n_obs=case.n_obs)[2]
+    obs = obs.copy()
+    obs[..., 2] = rng.uniform(-0.4, 0.4, obs.shape[:2]); obs[..., 3] = rng.uniform(3.0, 12.0, obs.shape[:2])
+    lo, hi = np.array(cfg.u_lo[:2]), np.array(cfg.u_hi[:2])
+    return x0, lo + rng.uniform(size=(PLANT_B, 2)) * (hi - lo), obs
+
+
+def plant_on_device(make_solver, case, cfg, rows, x0, u0, obs):
+    """[(x, obs) after step 1, after step 2] of ControlLoop.advance_device with the control held."""
+    bs = make_solver(cfg)
+    if case.tgrid is not None:
+        bs.set_time_grid(np.array(case.tgrid))
+    ps = bs.params(rows) if rows is not None else None
+    d_x, d_u, d_o = bs.device_array(x0.shape).upload(x0), bs.device_array(u0.shape).upload(u0), bs.device_array(obs.shape).upload(obs)
+    out = []
+    with bs.loop(PLANT_B, params=ps) as loop:
+        for _ in range(PLANT_STEPS):
+            loop.advance_device(d_x, d_u, d_o if case.move else None, first_only=case.move == 2, sync=True)
+            out.append((d_x.download(), d_o.download()))
+    for d in (d_x, d_u, d_o):
+        d.free()
+    if ps is not None:
+        ps.close()
+    bs.close()
+    return out
+
+
+def plant_recorded_obs(G, case, k):
+    """The obstacle rows [B,n_obs,6] after step k as tests/golden/plant_step.npz holds them: the inputs with x, y replaced."""
+    ob = G[plant_inputs_key(case) + "_obs"].copy()
+    ob[..., :2] = G["%s_obsxy%d" % (case.name, k)]
+    return ob
+
+
+def _field(cfg, rows, name):
+    """A config field as a scalar, or per instance [B, 1] where the case has a parameter set."""
+    return getattr(cfg, name) if rows is None else np.array([getattr(r, name) for r in rows])[:, None]
+
+
+def model_rhs(cfg, rows, x, u):
+    """f(x, u) of the configured model in numpy, rows of x / u per instance (kin.py:153-156, dyn.py:156-170)."""
+    c = lambda name: _field(cfg, rows, name)   # noqa: E731
+    x, u = x[:, :, None], u[:, :, None]
+    if cfg.model == _abi.MODEL_KIN:
+        return np.concatenate([x[:, 3] * np.cos(x[:, 2]), x[:, 3] * np.sin(x[:, 2]), x[:, 3] * np.tan(u[:, 0]) / c("veh_l"), u[:, 1]], axis=1)
+    phi, vx, vy, r, df, ax = x[:, 2], x[:, 3], x[:, 4], x[:, 5], u[:, 0], u[:, 1]
+    af, ar = df - (vy + c("veh_lf") * r) / vx, -(vy - c("veh_lr") * r) / vx
+    Fcf = -(c("Fymax_f") * 2 * c("aopt_f") / (c("aopt_f") ** 2 + af ** 2)) * af
+    Fcr = -(c("Fymax_r") * 2 * c("aopt_r") / (c("aopt_r") ** 2 + ar ** 2)) * ar
+    return np.concatenate([vx * np.cos(phi) - vy * np.sin(phi), vx * np.sin(phi) + vy * np.cos(phi), r, ax + r * vy,
+                           -r * vx + 2.0 / c("veh_m") * (Fcf * np.cos(df) + Fcr), 2.0 / c("veh_Iz") * (c("veh_lf") * Fcf - c("veh_lr") * Fcr)], axis=1)
+
+
+def plant_step(cfg, rows, x, u, obs, dt, move):
+    """(x, obs) one step on: Euler or classical RK4 as cfg.integrator says, the control held; obstacles as `move` says."""
+    k1 = model_rhs(cfg, rows, x, u)
+    if cfg.integrator == _abi.INT_RK4:
+        k2 = model_rhs(cfg, rows, x + 0.5 * dt * k1, u)
+        k3 = model_rhs(cfg, rows, x + 0.5 * dt * k2, u)
+        k4 = model_rhs(cfg, rows, x + dt * k3, u)
+        k1 = (k1 + 2.0 * k2 + 2.0 * k3 + k4) / 6.0
+    n = {0: 0, 1: obs.shape[1], 2: min(1, obs.shape[1])}[move]
+    obs = obs.copy()
+    obs[:, :n] = advance_obstacles(obs[:, :n], dt)
+    return x + dt * k1, obs
 
 
 # ---- per-step inputs: what a caller-supplied path or a set-point schedule looks like through the stepwise loop ------------------------

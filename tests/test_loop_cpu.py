@@ -1,6 +1,9 @@
 """The stepwise loop (mpcb_loop_*) without a GPU: the C ABI of the new entry points, the resource rows of its glue kernels, and the
 admission conditions of the scenarios tests/test_loop_gpu.py drives (tests/loop_cases.py): the oracle alone, run through the external
-plant with its own outputs, solves enough of every scenario for a comparison against it to mean something."""
+plant with its own outputs, solves enough of every scenario for a comparison against it to mean something.  And csrc/mpcb_plant.h, the
+header every glue kernel of the closed loop is built from, compiled for the host (tests/emu, emu.advance): hold rule, shift and counters
+equal to the numpy bookkeeping of tests/loop_cases.py, plant step and obstacle move within 1e-10 of its numpy expressions and of the
+plant steps recorded on the MI355X (tests/golden/plant_step.npz)."""
 import ctypes as C
 import os
 import re
@@ -9,7 +12,10 @@ import numpy as np
 import pytest
 
 from mpc_motion_planning_amd import _abi, _lib
+from mpc_motion_planning_amd import scenes
+from mpc_motion_planning_amd.solver import default_config
 from tests import config_cases as cc, loop_cases as lc
+from tests.emu import emu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -112,3 +118,133 @@ def test_oracle_alone_solves_enough_of_the_per_step_input_runs(oracle_mod, name)
     assert share >= lc.MIN_SOLVED_SHARE
     if name == "xs_switches_lane":
         assert not np.array_equal(log[lc.SWITCH_STEP]["xs"], log[lc.SWITCH_STEP - 1]["xs"])
+
+
+# ---- csrc/mpcb_plant.h on the host ---------------------------------------------------------------------------------------------------
+TWIN_B = 8
+EVERY_STATUS = np.array([_abi.ST_SOLVED, _abi.ST_MAXITER, _abi.ST_LINESEARCH, _abi.ST_INFEASIBLE_X0, _abi.ST_NUMERIC, _abi.ST_INFEASIBLE,
+                         _abi.ST_RESTO_FAILED, _abi.ST_ACCEPTABLE], np.int32)
+PLANT_TOL = 1e-10            # the bound tests/test_gpu_parity.py and tests/test_config_gpu.py put on the plant step against numpy
+KIN, DYN = _abi.MODEL_KIN, _abi.MODEL_DYN
+
+
+def _twin_inputs(model, n_obs, seed=5):
+    """(x0, u-box-respecting z factory, obs) for TWIN_B instances: sampled states (the dynamic ones with lateral speed and yaw rate),
+    obstacles with headings and speeds that are not zero."""
+    rng = np.random.default_rng(seed)
+    if model == DYN:
+        x0 = scenes.sample_c4(TWIN_B, seed=seed, n_obs=1)[0]
+        x0[:, 4:] = rng.uniform(-0.3, 0.3, (TWIN_B, 2))
+    else:
+        x0 = scenes.sample_c2(TWIN_B, seed=seed)[0]
+    obs = np.zeros((TWIN_B, n_obs, 6))
+    obs[..., :2] = rng.uniform(0.0, 60.0, (TWIN_B, n_obs, 2)); obs[..., 2] = rng.uniform(-0.4, 0.4, (TWIN_B, n_obs))
+    obs[..., 3] = rng.uniform(3.0, 12.0, (TWIN_B, n_obs)); obs[..., 4:] = (4.8, 1.8)
+    return x0, obs, rng
+
+
+def _plans(cfg, rng):
+    """(z, w) [B,nz]: random entries, the controls inside the config's box."""
+    lo, hi = np.array(cfg.u_lo[:2]), np.array(cfg.u_hi[:2])
+    out = []
+    for _ in range(2):
+        p = rng.normal(size=(TWIN_B, cfg.nz()))
+        p[:, :2 * cfg.N] = (lo + rng.uniform(size=(TWIN_B, cfg.N, 2)) * (hi - lo)).reshape(TWIN_B, -1)
+        out.append(p)
+    return out
+
+
+@pytest.mark.parametrize("in_place", [False, True], ids=["z", "in_place"])
+@pytest.mark.parametrize("hold", [False, True], ids=["apply", "hold"])
+@pytest.mark.parametrize("n", [1, 2, 30])
+@pytest.mark.parametrize("model", [KIN, DYN], ids=["kin", "dyn"])
+def test_twin_hold_rule_shift_and_counters_equal_the_numpy_bookkeeping(model, n, hold, in_place):
+    """One instance per status code.  in_place: the plan handed over IS the warm start (what a held plan is), for every instance."""
+    cfg = default_config(model=model, N=n, n_obs=0)
+    x0, _, rng = _twin_inputs(model, 0)
+    z, w = _plans(cfg, rng)
+    counters = (np.arange(TWIN_B, dtype=np.int32), 2 * np.arange(TWIN_B, dtype=np.int32))
+    got = emu.advance(cfg, None if in_place else z, x0, w, EVERY_STATUS, hold=hold, counters=counters)
+    plan = lc.executed_plan(w, w if in_place else z, EVERY_STATUS, hold)
+    assert np.array_equal(got["u0"], plan[:, :2])
+    assert np.array_equal(got["w"], lc.shift_plan(plan, n=n, nx=cfg.nx()))
+    assert np.array_equal(got["n_steps"], counters[0] + 1)
+    assert np.array_equal(got["n_failed"], counters[1] + ~lc.solved(EVERY_STATUS))
+    if hold and not in_place:
+        assert not np.array_equal(plan[1], z[1]) and np.array_equal(plan[0], z[0]) and np.array_equal(plan[7], z[7])      # the rule is seen
+    x1, _ = lc.plant_step(cfg, None, x0, plan[:, :2], np.zeros((TWIN_B, 0, 6)), cfg.T, 0)
+    assert np.abs(got["x0"] - x1).max() <= PLANT_TOL
+
+
+@pytest.mark.parametrize("move", [0, 1, 2], ids=["none", "all", "first"])
+@pytest.mark.parametrize("n_obs", [0, 1, 3])
+@pytest.mark.parametrize("model,integrator", [(KIN, _abi.INT_EULER), (KIN, _abi.INT_RK4), (DYN, _abi.INT_EULER)], ids=["kin_euler", "kin_rk4", "dyn_euler"])
+def test_twin_plant_step_and_obstacle_move_against_numpy(model, integrator, n_obs, move):
+    cfg = default_config(model=model, N=2, n_obs=n_obs); cfg.integrator = integrator
+    x0, obs, rng = _twin_inputs(model, n_obs)
+    z, w = _plans(cfg, rng)
+    got = emu.advance(cfg, z, x0, w, np.zeros(TWIN_B, np.int32), obs=obs, move_obs=move, T=0.08)
+    x1, ob1 = lc.plant_step(cfg, None, x0, z[:, :2], obs, 0.08, move)
+    assert np.abs(got["x0"] - x1).max() <= PLANT_TOL and np.abs(got["x0"] - x0).max() > 1e-2
+    assert np.abs(got["obs"] - ob1).max(initial=0.0) <= PLANT_TOL
+    moved = (got["obs"] != obs).any(axis=(0, 2))
+    assert moved.tolist() == [move == 1 or (move == 2 and j == 0) for j in range(n_obs)]
+    assert np.array_equal(got["obs"][..., 2:], obs[..., 2:])
+    if integrator == _abi.INT_RK4:                                # the other integrator would be seen
+        cfg.integrator = _abi.INT_EULER
+        assert np.abs(lc.plant_step(cfg, None, x0, z[:, :2], obs, 0.08, move)[0] - got["x0"]).max() > 1e-6
+
+
+def test_twin_two_interleaved_wheelbases():
+    cfg = default_config(N=2, n_obs=0)
+    other = cfg.copy(); other.veh_l = 3.1
+    rows = [cfg, other] * (TWIN_B // 2)
+    x0, _, rng = _twin_inputs(KIN, 0)
+    z, w = _plans(cfg, rng)
+    st = np.zeros(TWIN_B, np.int32)
+    got, plain = emu.advance(cfg, z, x0, w, st, cfgs=rows), emu.advance(cfg, z, x0, w, st)
+    x1, _ = lc.plant_step(cfg, rows, x0, z[:, :2], np.zeros((TWIN_B, 0, 6)), cfg.T, 0)
+    assert np.abs(got["x0"] - x1).max() <= PLANT_TOL
+    assert np.array_equal(got["x0"][0::2], plain["x0"][0::2]) and np.abs(got["x0"][1::2, 2] - plain["x0"][1::2, 2]).min() > 1e-6
+
+
+@pytest.mark.parametrize("step", [0, 3], ids=["first_step", "last_step"])
+def test_twin_histories(step):
+    """Row step + 1 of x_hist and row step of u_hist are written and nothing else of them; without histories the rest is the same."""
+    steps = 4
+    cfg = default_config(model=DYN, N=2, n_obs=0)
+    x0, _, rng = _twin_inputs(DYN, 0)
+    z, w = _plans(cfg, rng)
+    status = np.tile(EVERY_STATUS[:, None], (1, steps))
+    xh, uh = rng.normal(size=(TWIN_B, steps + 1, 6)), rng.normal(size=(TWIN_B, steps, 2))
+    got = emu.advance(cfg, z, x0, w, status, step=step, hold=True, x_hist=xh, u_hist=uh)
+    bare = emu.advance(cfg, z, x0, w, status, step=step, hold=True)
+    assert bare["x_hist"] is None and bare["u_hist"] is None
+    for k in ("x0", "w", "u0"):
+        assert np.array_equal(got[k], bare[k]), k
+    assert np.array_equal(got["x_hist"][:, step + 1], got["x0"]) and np.array_equal(got["u_hist"][:, step], got["u0"])
+    keep_x, keep_u = np.arange(steps + 1) != step + 1, np.arange(steps) != step
+    assert np.array_equal(got["x_hist"][:, keep_x], xh[:, keep_x]) and np.array_equal(got["u_hist"][:, keep_u], uh[:, keep_u])
+
+
+@pytest.mark.parametrize("case", lc.PLANT_CASES, ids=lc.ids(lc.PLANT_CASES))
+def test_twin_and_numpy_against_the_recorded_plant_steps(case):
+    """tests/golden/plant_step.npz: ControlLoop.advance_device on the MI355X before the header existed."""
+    G = np.load(os.path.join(ROOT, "tests", "golden", "plant_step.npz"))
+    cfg, rows = lc.plant_configs(case, default_config)
+    key = lc.plant_inputs_key(case)
+    x, u, ob = G[key + "_x0"], G[key + "_u0"], G[key + "_obs"]
+    assert x.shape == (lc.PLANT_B, cfg.nx()) and ob.shape == (lc.PLANT_B, case.n_obs, 6)
+    xn, obn = x, ob
+    dt = cfg.T if case.tgrid is None else case.tgrid[0]
+    plan = np.zeros((lc.PLANT_B, cfg.nz())); plan[:, :2] = u; plan[:, 2:4] = u          # shifted, the plan keeps its first control
+    for k in range(1, lc.PLANT_STEPS + 1):
+        got = emu.advance(cfg, plan, x, plan, np.zeros(lc.PLANT_B, np.int32), obs=ob, move_obs=case.move, T=dt, cfgs=rows)
+        assert np.array_equal(got["u0"], u)
+        x, ob = got["x0"], got["obs"]
+        xn, obn = lc.plant_step(cfg, rows, xn, u, obn, dt, case.move)
+        want_x, want_ob = G["%s_x%d" % (case.name, k)], lc.plant_recorded_obs(G, case, k)
+        print("%s step %d: twin %.2e / %.2e, numpy %.2e / %.2e from the recording (state / obstacles)" % (
+            case.name, k, np.abs(x - want_x).max(), np.abs(ob - want_ob).max(), np.abs(xn - want_x).max(), np.abs(obn - want_ob).max()))
+        assert np.abs(x - want_x).max() <= PLANT_TOL and np.abs(ob - want_ob).max() <= PLANT_TOL
+        assert np.abs(xn - want_x).max() <= PLANT_TOL and np.abs(obn - want_ob).max() <= PLANT_TOL

@@ -7,6 +7,7 @@ the teacher-forced reference loop of tests/loop_cases.py, compared with agree() 
 solves of a run: status agreement >= 0.98, trajectories within 1e-5 inside the basin, at most other_basin_allowance() beyond.
 Every test: B <= 64, <= 8 steps."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -145,6 +146,24 @@ def test_parameter_set_of_two_interleaved_configs_equals_closed_loop_params(gpu_
     bs.close()
     assert differing(got, want) == []
     assert np.abs(got["x_hist"][which == 1] - plain["x_hist"][which == 1]).max() > 1e-4       # the other wheelbase is seen, by solve and plant
+
+
+def test_advance_device_returns_the_recorded_plant_steps_bit_for_bit(gpu_solver_factory):
+    """tests/golden/plant_step.npz holds ControlLoop.advance_device from the build before the glue kernels were rebuilt on
+    csrc/mpcb_plant.h: since then both sides of the comparisons above are made of the same functions, and this is what ties them to
+    the bits of the kernels they replaced.  Every case of lc.PLANT_CASES, 64 instances, two steps in a row."""
+    G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plant_step.npz"))
+    bad = []
+    for case in lc.PLANT_CASES:
+        cfg, rows = lc.plant_configs(case, default_config)
+        key = lc.plant_inputs_key(case)
+        got = lc.plant_on_device(gpu_solver_factory, case, cfg, rows, G[key + "_x0"], G[key + "_u0"], G[key + "_obs"])
+        assert len(got) == lc.PLANT_STEPS
+        for k, (x, ob) in enumerate(got, start=1):
+            want_x, want_ob = G["%s_x%d" % (case.name, k)], lc.plant_recorded_obs(G, case, k)
+            print("%s step %d: state %.2e, obstacles %.2e from the recording" % (case.name, k, np.abs(x - want_x).max(), np.abs(ob - want_ob).max()))
+            bad += ["%s step %d %s" % (case.name, k, n) for n, a, b in (("x", x, want_x), ("obs", ob, want_ob)) if not bits(a, b)]
+    assert bad == []
 
 
 # ---- 2. external plant, against the oracle --------------------------------------------------------------------------------------------------
