@@ -175,7 +175,9 @@ int mpcb_dims(const mpcb_config* cfg, int32_t* nx, int32_t* nz, int32_t* ng);
 
 int mpcb_device_count(void);
 
-/* Create a solver for one NLP structure on HIP device `device` (replaces ca.nlpsol(...), kin.py:254). */
+/* Create a solver for one NLP structure on HIP device `device` (replaces ca.nlpsol(...), kin.py:254).
+ * MPCB_RESTO_IN_LAUNCH=0 in the environment at this call: the handle runs every restoration phase in a launch of its own instead of
+ * inside the lean launch (same results, for A/B timing). */
 int mpcb_create(const mpcb_config* cfg, int32_t device, mpcb_handle** out);
 int mpcb_destroy(mpcb_handle* h);
 const char* mpcb_last_error(const mpcb_handle* h);   /* h may be NULL: last creation error */

@@ -45,6 +45,18 @@ __device__ __forceinline__ bool mpcb_second_attempt_here(const MpcbKArgs& a, int
   return st != MPCB_ST_SOLVED && st != MPCB_ST_ACCEPTABLE && st != MPCB_ST_INFEASIBLE_X0;
 }
 
+// The restoration phase inside the lean launch (mpcbd::restores_here, mpcb_dispatch.h): the instantiations that have it ask, after their
+// last attempt, whether the launch was told to restore here and this instance has just ended with MPCB_ST_NEEDS_RESTO; the same wave
+// then runs the restoration instantiation on the same LDS, which reads z, the status and the hand-over record back from memory as the
+// restoration launch does.  (The flag is read late, from the argument block: nothing of it is alive during the solve.)
+template <int NOBS, bool GEN, bool RK4> constexpr bool mpcb_kin_restores = mpcbd::restores_here(MPCB_MODEL_KIN, NOBS, GEN, RK4);
+__device__ __forceinline__ bool mpcb_resto_here(const MpcbKArgs& a, int b) {
+  const MpcbKArgs& al = *wv::late_args(a);
+  if (!al.resto_here || !al.status) return false;
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");          // the status lane 0 has just stored, with z and the hand-over record
+  return __builtin_nontemporal_load(al.status + (size_t)b * al.st_stride) == MPCB_ST_NEEDS_RESTO;
+}
+
 template <int NOBS, bool GEN = false, bool RK4 = false>
 __global__ __launch_bounds__(64, MPCB_WAVES_PER_SIMD) void mpcb_kernel_kin(const MpcbKArgs a) {
   extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
@@ -58,6 +70,9 @@ __global__ __launch_bounds__(64, MPCB_WAVES_PER_SIMD) void mpcb_kernel_kin(const
     }
   } else {
     mpcb_solve_kin<NOBS, GEN, false, RK4>(a, (int)blockIdx.x, mpcb_lds, a.pass);
+  }
+  if constexpr (mpcb_kin_restores<NOBS, GEN, RK4>) {
+    if (mpcb_resto_here(a, (int)blockIdx.x)) mpcb_solve_kin<NOBS, GEN, true, RK4>(a, (int)blockIdx.x, mpcb_lds, MPCB_PASS_RESTO);
   }
 }
 
@@ -83,6 +98,9 @@ __global__ __launch_bounds__(64, MPCB_WAVES_PER_SIMD) void mpcb_track_kin(const 
     }
   } else {
     mpcb_solve_kin<NOBS, GEN, false, RK4, true>(a, (int)blockIdx.x, mpcb_lds, a.pass);
+  }
+  if constexpr (mpcb_kin_restores<NOBS, GEN, RK4>) {
+    if (mpcb_resto_here(a, (int)blockIdx.x)) mpcb_solve_kin<NOBS, GEN, true, RK4, true>(a, (int)blockIdx.x, mpcb_lds, MPCB_PASS_RESTO);
   }
 }
 
@@ -131,6 +149,9 @@ __global__ __launch_bounds__(64, MPCB_WAVES_PER_SIMD) void mpcb_param_kin(const 
     }
   } else {
     mpcb_solve_kin<NOBS, false, false, false, false, true>(a, (int)blockIdx.x, mpcb_lds, a.pass);
+  }
+  if constexpr (mpcb_kin_restores<NOBS, false, false>) {
+    if (mpcb_resto_here(a, (int)blockIdx.x)) mpcb_solve_kin<NOBS, false, true, false, false, true>(a, (int)blockIdx.x, mpcb_lds, MPCB_PASS_RESTO);
   }
 }
 
@@ -444,6 +465,7 @@ struct mpcb_handle {
   std::vector<mpcb_params*> params;                    // live parameter sets of this handle (mpcb_destroy frees what the caller left)
   std::vector<mpcb_loop*> loops;                       // live stepwise loops of this handle (freed at mpcb_destroy likewise)
   int loops_created = 0;                               // the next loop's id
+  bool resto_in_launch = true;                         // MPCB_RESTO_IN_LAUNCH=0 at mpcb_create: every restoration phase in a launch of its own (A/B runs)
 };
 
 namespace {
@@ -671,7 +693,10 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
   for (int i = 0; i < plan.n; ++i) {
     a.pass = plan.pass[i];
     const bool resto = a.pass == MPCB_PASS_RESTO;
-    int rc = mpcbd::visit(v, resto, [&](auto inst) { return launch_kernel(h, stream, kernel_of(inst), a, lds[resto]); });
+    // a lean launch that runs the restoration phase of its instances itself gets the restoration layout's LDS; the restoration launch
+    // after it then finds no instance to continue
+    a.resto_here = mpcbd::resto_in_launch(v, h->cfg.N, plan, i, h->resto_in_launch ? -1 : 0) ? 1 : 0;
+    int rc = mpcbd::visit(v, resto, [&](auto inst) { return launch_kernel(h, stream, kernel_of(inst), a, lds[resto || a.resto_here]); });
     if (rc != MPCB_OK) return rc;
     HIP_TRY(h, hipGetLastError());
   }
@@ -1015,6 +1040,7 @@ int mpcb_create(const mpcb_config* cfg, int32_t device, mpcb_handle** out) {
   if (device < 0 || device >= ndev) return fail(nullptr, MPCB_E_INVALID, "device %d outside 0..%d", device, ndev - 1);
   mpcb_handle* h = new mpcb_handle();
   h->cfg = *cfg; h->device = device;
+  { const char* e = std::getenv("MPCB_RESTO_IN_LAUNCH"); h->resto_in_launch = !(e && e[0] == '0' && e[1] == 0); }
   int nx, nz, ng; mpcb_dims(cfg, &nx, &nz, &ng);
   h->nx = nx; h->nz = nz; h->ng = ng;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {

@@ -1,6 +1,7 @@
-// mpcb_dispatch.h — which solve instantiation serves a config, how much LDS it gets, whether it fuses its second attempt, and in which
-// order the passes of a solve run.  Host only, plain C++17; included behind the kernel headers by mpcb_api.hip (which launches what this
-// header selects) and by tests/emu/wave_emu.cpp (which steps the same selection on the CPU).  The policy is stated here and nowhere else.
+// mpcb_dispatch.h — which solve instantiation serves a config, how much LDS it gets, whether it fuses its second attempt, in which
+// order the passes of a solve run, and which lean launch runs the restoration phase of its instances itself.  Host only, plain C++17;
+// included behind the kernel headers by mpcb_api.hip (which launches what this header selects) and by tests/emu/wave_emu.cpp and
+// tests/emu_resto/resto_emu.cpp (which step the same selection on the CPU).  The policy is stated here and nowhere else.
 #pragma once
 
 #include <cstddef>
@@ -102,6 +103,37 @@ inline Plan pass_plan(const mpcb_config& c, bool start_given, bool fused) {
     if (c.restoration) p.pass[p.n++] = MPCB_PASS_RESTO;
   }
   return p;
+}
+
+// ---- the restoration phase inside the lean launch ------------------------------------------------------------------------------------
+// The restoration pass continues a few instances in a hundred (C2: about 100 of 4096), yet as a launch of its own it can only begin
+// when the slowest instance of the lean launch has finished, and it holds its stream for the length of its own slowest instance.  Where
+// this rule says yes, the wave of the lean launch that ends with MPCB_ST_NEEDS_RESTO calls the restoration instantiation itself, at once
+// and on the same LDS; that instantiation reads z, the status and the hand-over record back from memory exactly as in a launch of its
+// own, so the results are the same by construction.  The MPCB_PASS_RESTO launch of the plan stays and finds no instance to continue.
+// Only the Euler kin<0|1> kernels without GEN (plain, tracking, per-instance) do this: their restoration twins need no scratch, those of
+// kin<3> and dyn<1|3> spill 230-600 B and would take the lean kernels' zero scratch with them.  -DMPCB_NO_RESTO_IN_LAUNCH: no
+// instantiation does (A/B builds).  The kernels' `if constexpr` (mpcb_api.hip) and the host's launch both read restores_here().
+#ifdef MPCB_NO_RESTO_IN_LAUNCH
+constexpr int RESTO_HERE_NOBS_MAX = -1;
+#else
+constexpr int RESTO_HERE_NOBS_MAX = 1;
+#endif
+constexpr bool restores_here(int model, int nobs, bool gen, bool rk4) {
+  return model == MPCB_MODEL_KIN && nobs <= RESTO_HERE_NOBS_MAX && !gen && !rk4;
+}
+constexpr bool restores_here(const Variant& v) { return restores_here(v.model, v.nobs, v.gen, v.rk4); }
+
+// workgroups of one wave a CU holds: one per SIMD (the solve kernels' registers), and as many as its LDS has room for
+constexpr int wgs_per_cu(size_t lds) { return lds == 0 || LDS_MAX_BYTES / lds >= 4 ? 4 : (int)(LDS_MAX_BYTES / lds); }
+
+// Does launch i of the plan run the restoration phase of its instances itself?  The instantiation has the code, the plan's next pass
+// is the restoration pass, and the restoration layout's LDS leaves the lean launch as many workgroups per CU as its own layout
+// (N = 30: 4 and 4; N = 50: 3 and 2, so there the passes stay apart).  force: 0 never, 1 without the LDS condition (tests/emu_resto), -1 the rule.
+inline bool resto_in_launch(const Variant& v, int N, const Plan& plan, int i, int force = -1) {
+  if (force == 0 || !restores_here(v)) return false;
+  if (plan.pass[i] == MPCB_PASS_RESTO || i + 1 >= plan.n || plan.pass[i + 1] != MPCB_PASS_RESTO) return false;
+  return force == 1 || wgs_per_cu(lds_bytes(v, N, true)) >= wgs_per_cu(lds_bytes(v, N, false));
 }
 
 // ---- run-time variant -> compile-time template arguments ------------------------------------------------------------------------------

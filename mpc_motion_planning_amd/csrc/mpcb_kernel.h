@@ -46,7 +46,8 @@ struct MpcbKArgs {
   double* trace;   // optional: [max_iter + 1][8] log of instance trace_instance (debug / parity tests)
   const double* xref;  // [B][N][4] per-stage reference of the tracking kernels (mpcb_solve_ref): row i replaces xs in stage i's cost; NULL elsewhere
   const mpcb_config* cfgs;  // [B] per-instance configs of the PARAMS kernels (mpcb_solve_params): validated rows, structurally equal to cfg; NULL elsewhere.
-                            // The last member: the offsets of every field above are those of the kernels that never read it.
+  int32_t resto_here;       // this lean launch runs the restoration phase of its MPCB_ST_NEEDS_RESTO instances itself (mpcbd::resto_in_launch); read by
+                            // the kernel wrappers only.  New members go last: the offsets of every field above are those of the kernels that never read them.
 };
 
 // MPCB_STAMPS (diagnostic build only, never shipped): overwrite trace columns 4..7 with cycle counts of the phases of
