@@ -435,6 +435,10 @@ int mpcb_evaluate_device(mpcb_handle* h, int32_t B, const mpcb_params* p,
                          const double* d_lam_g, const double* d_lam_x,
                          double* d_obj, double* d_g, double* d_grad_lag, double* d_res, int32_t sync);
 
+/* ---- multi-start solve: K starts per instance, the best solution kept on the device: mpcb_solve_multi and mpcb_solve_multi_device.
+ * Part of this ABI; the two declarations and their description are kept in a file of their own, included here. */
+#include "mpcbatch_multi.h"
+
 /* ---- scene generation on the device -----------------------------------------------------------------------
  * Counter-based random scenes (Philox4x32-10 keyed by `seed`, counter = global scene index): scene i is the same whichever GPU,
  * batch or chunk it is generated in, so 8 GPUs draw disjoint slices of one Monte-Carlo population from (seed, first_index).

@@ -17,7 +17,7 @@ __all__ = ["MpcbConfig", "BatchSolver", "default_config", "shift", "shift_moveme
 
 
 def __getattr__(name):   # the solver front-end needs the built library; import it lazily
-    if name in ("BatchSolver", "default_config", "DeviceArray", "dims", "device_count", "model_rhs"):
+    if name in ("BatchSolver", "default_config", "DeviceArray", "dims", "device_count", "model_rhs", "turn_starts"):
         from . import solver
         return getattr(solver, name)
     raise AttributeError(name)

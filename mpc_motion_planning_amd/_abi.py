@@ -23,6 +23,7 @@ OBSMOVE_STATIC, OBSMOVE_PREDICTED, OBSMOVE_CURRENT = 0, 1, 2
 NX_MAX, NU, NOBS_MAX, N_MAX = 6, 2, 8, 63
 UNIQUE_ID_BYTES = 128
 SCENES_C2, SCENES_C3, SCENES_C4 = 2, 3, 4
+MULTI_MAX = 8     # most starts per instance of mpcb_solve_multi
 EVAL_COLS = 7
 EVAL_NAMES = ("feas_g", "feas_x", "h_min", "stationarity", "compl", "sign", "lam_scale")     # columns of mpcb_evaluate's res
 

@@ -80,6 +80,15 @@ SIGNATURES = {
     "mpcb_model_rhs": (C.c_int, [C.POINTER(MpcbConfig), _PD, _PD, _PD]),
 }
 
+# the functions include/mpcbatch_multi.h declares (tests/test_multi_cpu.py checks)
+MULTI_SIGNATURES = {
+    "mpcb_solve_multi": (C.c_int, [_H, C.c_int32, C.c_int32, _PD, _PD, _PD, C.c_int32, _PD, _PD, C.c_double, C.c_double,
+                                   _PD, _PD, _PI, _PI, _PD, _PD, _PD, _PI, _PI, _PI, _PD, _PD, _PI, _PI]),
+    "mpcb_solve_multi_device": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, _PD, C.c_double, C.c_double,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+}
+
 
 class MpcbError(RuntimeError):
     def __init__(self, code, msg):
@@ -96,7 +105,7 @@ def lib():
             raise ImportError("libmpcbatch.so is not built (%s missing); there is no CPU fallback. "
                               "Build it with: make -C mpc_motion_planning_amd/csrc" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(MULTI_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -20,6 +20,7 @@
 #include "mpcb_kernel_dyn.h"
 #include "mpcb_dispatch.h"
 #include "mpcb_eval.h"
+#include "mpcb_multi.h"
 #include "mpcb_plant.h"
 
 #ifndef MPCB_WAVES_PER_SIMD
@@ -191,6 +192,10 @@ __global__ __launch_bounds__(64) void mpcb_eval(const MpcbEvalArgs a) {
   extern __shared__ __attribute__((aligned(16))) double mpcb_lds[];
   ::mpcb_eval<NX, PARAMS>(a, (int)blockIdx.x, mpcb_lds);
 }
+
+// The glue of the multi-start solve (mpcb_solve_multi, mpcb_multi.h): one wave per expanded instance / per instance, no LDS.
+__global__ __launch_bounds__(64) void mpcb_multi_expand(const MpcbMultiArgs a) { mpcbm::expand(a, (int)blockIdx.x); }
+__global__ __launch_bounds__(64) void mpcb_multi_select(const MpcbMultiArgs a) { mpcbm::select(a, (int)blockIdx.x); }
 
 // ---- the closed loop between two solves: index arithmetic around the per-instance pieces of mpcb_plant.h ---------------------------------
 // One thread per instance (tiny, HBM-bound, runs between two solves of the closed loop).
@@ -435,6 +440,9 @@ struct mpcb_handle {
   int nx = 4, nz = 0, ng = 0;
   // scratch for the host-pointer entries
   void* d_buf = nullptr; size_t d_cap = 0;
+  // workspace of the multi-start solve (mpcb_solve_multi*): the expanded batch and what the caller did not ask to see of its results;
+  // grows with the largest K * B seen, freed in mpcb_destroy
+  void* d_multi = nullptr; size_t multi_cap = 0;
   // timing: a ring of event pairs created once; a pair is harvested (synchronised, accumulated) before it is reused
   static constexpr int EV_RING = 256;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // EV_RING pairs, created on first use
@@ -1057,6 +1065,7 @@ int mpcb_destroy(mpcb_handle* h) {
   collect_timing(h);
   for (auto& p : h->ev) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
   if (h->d_buf) (void)hipFree(h->d_buf);
+  if (h->d_multi) (void)hipFree(h->d_multi);
   for (auto* p : h->params) { if (p->d_cfgs) (void)hipFree(p->d_cfgs); delete p; }
   for (auto* p : h->peers) mpcb_destroy(p);
   if (h->comm) { const Rccl* R = rccl(); if (R) (void)R->CommDestroy(h->comm); }
@@ -1634,6 +1643,179 @@ int mpcb_evaluate(mpcb_handle* h, int32_t B, const mpcb_params* p, const double*
   if (g) HIP_TRY(h, hipMemcpyAsync(g, d.g, nb * ng * 8, hipMemcpyDeviceToHost, s));
   if (grad_lag) HIP_TRY(h, hipMemcpyAsync(grad_lag, d.grad, nb * nz * 8, hipMemcpyDeviceToHost, s));
   if (res) HIP_TRY(h, hipMemcpyAsync(res, d.res, nb * MPCB_EVAL_COLS * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return MPCB_OK;
+}
+
+// ---- multi-start solve: K starts per instance, the best solution kept on the device ------------------------------------------------
+// The pointers of one multi-start call in the order the C entries list them (device pointers for multi_on_device, the caller's host
+// pointers in mpcb_solve_multi); controls is a host array in both.
+struct MultiCall {
+  int32_t B = 0, K = 0; const double *x0 = nullptr, *xs = nullptr, *obs = nullptr; int32_t obs_kind = MPCB_OBSIN_STATIC; const double* z0 = nullptr;
+  const double* controls = nullptr; double obj_margin = 0, basin_tol = 0;
+  double *z = nullptr, *obj = nullptr; int32_t *status = nullptr, *iters = nullptr; double *kkt = nullptr, *lam_g = nullptr, *lam_x = nullptr;
+  int32_t *which = nullptr, *n_ok = nullptr, *n_basins = nullptr;
+  double *z_all = nullptr, *obj_all = nullptr; int32_t *status_all = nullptr, *iters_all = nullptr;
+};
+
+// every refusal of mpcb_solve_multi / mpcb_solve_multi_device: before anything is uploaded or launched
+static int check_multi(mpcb_handle* h, const MultiCall& m) {
+  if (m.K < 1 || m.K > MPCB_MULTI_MAX) return fail(h, MPCB_E_INVALID, "K = %d outside 1..%d", m.K, MPCB_MULTI_MAX);
+  if (m.B < 0) return fail(h, MPCB_E_INVALID, "B = %d is negative", m.B);
+  if ((int64_t)m.B * m.K > (int64_t)std::numeric_limits<int32_t>::max())
+    return fail(h, MPCB_E_INVALID, "K * B = %lld exceeds the largest grid of one launch", (long long)m.B * m.K);
+  if (!m.controls && !(m.K == 1 && m.z0)) return fail(h, MPCB_E_INVALID, "controls is NULL (allowed only for K = 1 with a start vector z0)");
+  if (m.controls) for (int i = 0; i < 2 * m.K; ++i)
+    if (!std::isfinite(m.controls[i])) return fail(h, MPCB_E_INVALID, "controls[%d][%d] is not finite", i / 2, i % 2);
+  if (!m.z) return fail(h, MPCB_E_INVALID, "z is NULL");
+  if (!(m.obj_margin >= 0.0) || !std::isfinite(m.obj_margin)) return fail(h, MPCB_E_INVALID, "obj_margin = %g must be finite and >= 0", m.obj_margin);
+  if (!(m.basin_tol >= 0.0) || !std::isfinite(m.basin_tol)) return fail(h, MPCB_E_INVALID, "basin_tol = %g must be finite and >= 0", m.basin_tol);
+  if (!m.x0 || !m.xs) return fail(h, MPCB_E_INVALID, "a required pointer is NULL (x0 and xs are required)");
+  if (h->cfg.n_obs > 0 && !m.obs) return fail(h, MPCB_E_INVALID, "n_obs = %d but obs is NULL", h->cfg.n_obs);
+  if (m.obs_kind != MPCB_OBSIN_STATIC && m.obs_kind != MPCB_OBSIN_PREDICTED) return fail(h, MPCB_E_INVALID, "unknown obs_kind %d", m.obs_kind);
+  if (!h->peers.empty()) return fail(h, MPCB_E_UNSUPPORTED, "the multi-start solve does not run on a device group (mpcb_set_devices)");
+  // what launch_solve would refuse, asked before the expansion is launched: every candidate is a solve with a start vector
+  mpcbd::Variant v;
+  { int rc = variant_or_fail(h, h->cfg, false, false, &v); if (rc != MPCB_OK) return rc; }
+  const mpcbd::Plan plan = mpcbd::pass_plan(h->cfg, true, mpcbd::fuses(v));
+  for (int i = 0; i < plan.n; ++i) {
+    const size_t need = mpcbd::lds_bytes(v, h->cfg.N, plan.pass[i] == MPCB_PASS_RESTO);
+    if (need > mpcbd::LDS_MAX_BYTES) return fail(h, MPCB_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", need);
+  }
+  return MPCB_OK;
+}
+
+// expand -> one ordinary solve of K * B instances -> select, everything resident on the handle's device, on the handle's own stream
+static int multi_on_device(mpcb_handle* h, const MultiCall& m) {
+  if (m.B == 0) return MPCB_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
+  const int nx = h->nx, nz = h->nz, ng = h->ng, N = h->cfg.N;
+  const size_t E = (size_t)m.B * m.K;
+  const size_t obs_row = (size_t)h->cfg.n_obs * 6 * (m.obs_kind == MPCB_OBSIN_PREDICTED ? N + 1 : 1);
+  MpcbMultiArgs a;
+  std::memset(&a, 0, sizeof a);
+  double* d_kkt_all = nullptr;
+  auto carve = [&](Carve& cv) {
+    a.x0_e = cv.take<double>(E * nx);
+    a.xs_e = cv.take<double>(E * nx);
+    a.obs_e = obs_row ? cv.take<double>(E * obs_row) : nullptr;
+    a.z0_e = cv.take<double>(E * nz);
+    a.z_all = m.z_all ? m.z_all : cv.take<double>(E * nz);           // where the caller passes a *_all pointer the solve writes there directly
+    a.obj_all = m.obj_all ? m.obj_all : cv.take<double>(E);
+    a.status_all = m.status_all ? m.status_all : cv.take<int32_t>(E);
+    a.iters_all = m.iters_all ? m.iters_all : cv.take<int32_t>(E);
+    d_kkt_all = m.kkt ? cv.take<double>(E * 4) : nullptr;
+    a.lam_g_all = m.lam_g ? cv.take<double>(E * ng) : nullptr;
+    a.lam_x_all = m.lam_x ? cv.take<double>(E * nz) : nullptr;
+  };
+  { Carve dry{nullptr}; carve(dry);
+    if (dry.bytes() > h->multi_cap) {
+      HIP_TRY(h, hipStreamSynchronize(h->stream));                    // an earlier call may still read the old workspace
+      if (h->d_multi) { HIP_TRY(h, hipFree(h->d_multi)); h->d_multi = nullptr; h->multi_cap = 0; }
+      HIP_TRY(h, hipMalloc(&h->d_multi, dry.bytes()));
+      h->multi_cap = dry.bytes();
+    } }
+  { Carve cv{(char*)h->d_multi}; carve(cv); }
+  a.kkt_all = d_kkt_all;
+  a.B = m.B; a.K = m.K; a.N = N; a.nx = nx; a.nz = nz; a.ng = ng; a.obs_row = (int32_t)obs_row;
+  if (m.controls) for (int i = 0; i < 2 * m.K; ++i) a.controls[i] = m.controls[i];
+  a.obj_margin = m.obj_margin; a.basin_tol = m.basin_tol;
+  a.x0 = m.x0; a.xs = m.xs; a.obs = obs_row ? m.obs : nullptr; a.z0 = m.z0;
+  a.z = m.z; a.obj = m.obj; a.kkt = m.kkt; a.lam_g = m.lam_g; a.lam_x = m.lam_x;
+  a.status = m.status; a.iters = m.iters; a.which = m.which; a.n_ok = m.n_ok; a.n_basins = m.n_basins;
+  const hipStream_t s = h->stream;
+  hipLaunchKernelGGL(mpcb_multi_expand, dim3((unsigned)E), dim3(64), 0, s, a);
+  HIP_TRY(h, hipGetLastError());
+  SolveArgs sv = solve_args((int32_t)E, a.x0_e, a.xs_e, a.obs_e, m.obs_kind, a.z0_e, const_cast<double*>(a.z_all), const_cast<double*>(a.obj_all),
+                            const_cast<int32_t*>(a.status_all), const_cast<int32_t*>(a.iters_all), d_kkt_all,
+                            const_cast<double*>(a.lam_g_all), const_cast<double*>(a.lam_x_all));
+  { int rc = solve_on_device(h, sv, 0); if (rc != MPCB_OK) return rc; }
+  hipLaunchKernelGGL(mpcb_multi_select, dim3((unsigned)m.B), dim3(64), 0, s, a);
+  HIP_TRY(h, hipGetLastError());
+  return MPCB_OK;
+}
+
+int mpcb_solve_multi_device(mpcb_handle* h, int32_t B, int32_t K, const double* d_x0, const double* d_xs, const double* d_obs, int32_t obs_kind,
+                            const double* d_z0, const double* controls, double obj_margin, double basin_tol,
+                            double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt, double* d_lam_g, double* d_lam_x,
+                            int32_t* d_which, int32_t* d_n_ok, int32_t* d_n_basins,
+                            double* d_z_all, double* d_obj_all, int32_t* d_status_all, int32_t* d_iters_all, int32_t sync) {
+  if (!h) return MPCB_E_INVALID;
+  MultiCall m;
+  m.B = B; m.K = K; m.x0 = d_x0; m.xs = d_xs; m.obs = d_obs; m.obs_kind = obs_kind; m.z0 = d_z0; m.controls = controls;
+  m.obj_margin = obj_margin; m.basin_tol = basin_tol;
+  m.z = d_z; m.obj = d_obj; m.status = d_status; m.iters = d_iters; m.kkt = d_kkt; m.lam_g = d_lam_g; m.lam_x = d_lam_x;
+  m.which = d_which; m.n_ok = d_n_ok; m.n_basins = d_n_basins;
+  m.z_all = d_z_all; m.obj_all = d_obj_all; m.status_all = d_status_all; m.iters_all = d_iters_all;
+  { int rc = check_multi(h, m); if (rc != MPCB_OK) return rc; }
+  { int rc = multi_on_device(h, m); if (rc != MPCB_OK) return rc; }
+  return sync ? mpcb_sync(h) : MPCB_OK;
+}
+
+int mpcb_solve_multi(mpcb_handle* h, int32_t B, int32_t K, const double* x0, const double* xs, const double* obs, int32_t obs_kind,
+                     const double* z0, const double* controls, double obj_margin, double basin_tol,
+                     double* z, double* obj, int32_t* status, int32_t* iters, double* kkt, double* lam_g, double* lam_x,
+                     int32_t* which, int32_t* n_ok, int32_t* n_basins,
+                     double* z_all, double* obj_all, int32_t* status_all, int32_t* iters_all) {
+  if (!h) return MPCB_E_INVALID;
+  MultiCall in;
+  in.B = B; in.K = K; in.x0 = x0; in.xs = xs; in.obs = obs; in.obs_kind = obs_kind; in.z0 = z0; in.controls = controls;
+  in.obj_margin = obj_margin; in.basin_tol = basin_tol;
+  in.z = z; in.obj = obj; in.status = status; in.iters = iters; in.kkt = kkt; in.lam_g = lam_g; in.lam_x = lam_x;
+  in.which = which; in.n_ok = n_ok; in.n_basins = n_basins;
+  in.z_all = z_all; in.obj_all = obj_all; in.status_all = status_all; in.iters_all = iters_all;
+  { int rc = check_multi(h, in); if (rc != MPCB_OK) return rc; }
+  if (B == 0) return MPCB_OK;
+  HIP_TRY(h, hipSetDevice(h->device));
+  { int rc = join_lanes(h); if (rc != MPCB_OK) return rc; }
+  const size_t nx = h->nx, nz = h->nz, ng = h->ng, N = h->cfg.N, nb = (size_t)B, E = nb * K;
+  const size_t n_obs_d = nb * h->cfg.n_obs * 6 * (obs_kind == MPCB_OBSIN_PREDICTED ? N + 1 : 1);
+  MultiCall d = in;
+  double *d_x0, *d_xs, *d_obs, *d_z0;
+  auto carve = [&](Carve& cv) {
+    d_x0 = cv.take<double>(nb * nx);
+    d_xs = cv.take<double>(nb * nx);
+    d_obs = n_obs_d ? cv.take<double>(n_obs_d) : nullptr;
+    d_z0 = z0 ? cv.take<double>(nb * nz) : nullptr;
+    d.z = cv.take<double>(nb * nz);
+    d.obj = obj ? cv.take<double>(nb) : nullptr;
+    d.status = status ? cv.take<int32_t>(nb) : nullptr;
+    d.iters = iters ? cv.take<int32_t>(nb) : nullptr;
+    d.kkt = kkt ? cv.take<double>(nb * 4) : nullptr;
+    d.lam_g = lam_g ? cv.take<double>(nb * ng) : nullptr;
+    d.lam_x = lam_x ? cv.take<double>(nb * nz) : nullptr;
+    d.which = which ? cv.take<int32_t>(nb) : nullptr;
+    d.n_ok = n_ok ? cv.take<int32_t>(nb) : nullptr;
+    d.n_basins = n_basins ? cv.take<int32_t>(nb) : nullptr;
+    d.z_all = z_all ? cv.take<double>(E * nz) : nullptr;
+    d.obj_all = obj_all ? cv.take<double>(E) : nullptr;
+    d.status_all = status_all ? cv.take<int32_t>(E) : nullptr;
+    d.iters_all = iters_all ? cv.take<int32_t>(E) : nullptr;
+  };
+  { Carve dry{nullptr}; carve(dry); int rc = ensure_scratch(h, dry.bytes()); if (rc != MPCB_OK) return rc; }
+  { Carve cv{(char*)h->d_buf}; carve(cv); }
+  d.x0 = d_x0; d.xs = d_xs; d.obs = d_obs; d.z0 = d_z0;
+  hipStream_t s = h->stream;
+  HIP_TRY(h, hipMemcpyAsync(d_x0, x0, nb * nx * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(d_xs, xs, nb * nx * 8, hipMemcpyHostToDevice, s));
+  if (d_obs) HIP_TRY(h, hipMemcpyAsync(d_obs, obs, n_obs_d * 8, hipMemcpyHostToDevice, s));
+  if (d_z0) HIP_TRY(h, hipMemcpyAsync(d_z0, z0, nb * nz * 8, hipMemcpyHostToDevice, s));
+  { int rc = multi_on_device(h, d); if (rc != MPCB_OK) return rc; }
+  HIP_TRY(h, hipMemcpyAsync(z, d.z, nb * nz * 8, hipMemcpyDeviceToHost, s));
+  if (obj) HIP_TRY(h, hipMemcpyAsync(obj, d.obj, nb * 8, hipMemcpyDeviceToHost, s));
+  if (status) HIP_TRY(h, hipMemcpyAsync(status, d.status, nb * 4, hipMemcpyDeviceToHost, s));
+  if (iters) HIP_TRY(h, hipMemcpyAsync(iters, d.iters, nb * 4, hipMemcpyDeviceToHost, s));
+  if (kkt) HIP_TRY(h, hipMemcpyAsync(kkt, d.kkt, nb * 4 * 8, hipMemcpyDeviceToHost, s));
+  if (lam_g) HIP_TRY(h, hipMemcpyAsync(lam_g, d.lam_g, nb * ng * 8, hipMemcpyDeviceToHost, s));
+  if (lam_x) HIP_TRY(h, hipMemcpyAsync(lam_x, d.lam_x, nb * nz * 8, hipMemcpyDeviceToHost, s));
+  if (which) HIP_TRY(h, hipMemcpyAsync(which, d.which, nb * 4, hipMemcpyDeviceToHost, s));
+  if (n_ok) HIP_TRY(h, hipMemcpyAsync(n_ok, d.n_ok, nb * 4, hipMemcpyDeviceToHost, s));
+  if (n_basins) HIP_TRY(h, hipMemcpyAsync(n_basins, d.n_basins, nb * 4, hipMemcpyDeviceToHost, s));
+  if (z_all) HIP_TRY(h, hipMemcpyAsync(z_all, d.z_all, E * nz * 8, hipMemcpyDeviceToHost, s));
+  if (obj_all) HIP_TRY(h, hipMemcpyAsync(obj_all, d.obj_all, E * 8, hipMemcpyDeviceToHost, s));
+  if (status_all) HIP_TRY(h, hipMemcpyAsync(status_all, d.status_all, E * 4, hipMemcpyDeviceToHost, s));
+  if (iters_all) HIP_TRY(h, hipMemcpyAsync(iters_all, d.iters_all, E * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));
   return MPCB_OK;
 }

@@ -53,6 +53,21 @@ def model_rhs(cfg, x, u):
     return out
 
 
+def turn_starts(K=3, steer=0.03, accel=0.0):
+    """The K constant-control starts of solve_multi, [K, 2] rows (steer, accel): straight on, then a slight turn to either side, then
+    twice that turn, ...:  [[0, a], [+s, a], [-s, a], [+2s, a], [-2s, a], ...] cut to K rows."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1")
+    rows = [[0.0, float(accel)]]
+    m = 1
+    while len(rows) < K:
+        rows.append([m * float(steer), float(accel)])
+        rows.append([-m * float(steer), float(accel)])
+        m += 1
+    return np.array(rows[:K], dtype=np.float64)
+
+
 def vary(cfg, B, **fields):
     """A ctypes array of B configs copied from `cfg`, with each named field set per instance from an array of shape [B] (scalar
     fields) or [B, k] (array fields of length k):  vary(cfg, B, Q=q[B,4], veh_l=l[B]).  An array field may be given fewer columns
@@ -484,6 +499,66 @@ class BatchSolver:
         else:
             check(lib().mpcb_solve_device_ref(self._h, B, p(d_x0), p(d_xs), p(d_x_ref), p(d_obs), obs_kind, p(d_z0), p(d_z), p(d_obj),
                                               p(d_status), p(d_iters), p(d_kkt), p(d_lam_g), p(d_lam_x), 1 if sync else 0), self._h)
+
+    # ----- multi-start solve (include/mpcbatch_multi.h) ------------------------------------------------------
+    @staticmethod
+    def _controls(controls):
+        """[K, 2] float64 rows of (steer, accel); None means turn_starts(3)."""
+        if controls is None:
+            return turn_starts(3)
+        c = np.ascontiguousarray(np.asarray(controls, dtype=np.float64))
+        if c.ndim != 2 or c.shape[1] != 2 or c.shape[0] < 1:
+            raise ValueError("controls must be [K, 2] rows of (steer, accel), got %s" % (c.shape,))
+        return c
+
+    def solve_multi(self, x0, xs, obs=None, z0=None, controls=None, multipliers=False, obj_margin=1e-9, basin_tol=1e-4, want_all=False):
+        """Every instance solved from K starts in one launch of K * B instances, the cheapest solution kept (mpcb_solve_multi).
+        controls [K,2] rows of (steer, accel) held over the horizon, None = turn_starts(3); z0 [B,nz] | None: the caller's start of
+        candidate 0, used verbatim.  A later candidate replaces the incumbent only if its objective is lower by more than
+        obj_margin * max(1, |obj|); two solutions count as one when they differ by at most basin_tol in every entry of z.
+        Returns the dict of solve_batch (the winner's z, obj, status, iters, kkt[, lam_g, lam_x]) plus which [B] (the winner's index),
+        n_ok [B] (candidates that solved) and n_basins [B] (distinct solutions found); with want_all also z_all [B,K,nz], obj_all,
+        status_all, iters_all [B,K]."""
+        x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0, dtype=np.float64)))
+        xs = np.ascontiguousarray(np.atleast_2d(np.asarray(xs, dtype=np.float64)))
+        B = x0.shape[0]
+        if x0.shape != (B, self.nx) or xs.shape != (B, self.nx):
+            raise ValueError("x0 and xs must be [B,%d]" % self.nx)
+        obs, kind = self._obs(obs, B)
+        if z0 is not None:
+            z0 = np.ascontiguousarray(np.asarray(z0, dtype=np.float64).reshape(B, self.nz))
+        c = self._controls(controls)
+        K = c.shape[0]
+        z = np.empty((B, self.nz)); obj = np.empty(B); st = np.empty(B, np.int32); it = np.empty(B, np.int32); kkt = np.empty((B, 4))
+        lam_g = np.empty((B, self.ng)) if multipliers else None
+        lam_x = np.empty((B, self.nz)) if multipliers else None
+        which = np.empty(B, np.int32); n_ok = np.empty(B, np.int32); n_basins = np.empty(B, np.int32)
+        z_all = np.empty((B, K, self.nz)) if want_all else None
+        obj_all = np.empty((B, K)) if want_all else None
+        st_all = np.empty((B, K), np.int32) if want_all else None
+        it_all = np.empty((B, K), np.int32) if want_all else None
+        check(lib().mpcb_solve_multi(self._h, B, K, dptr(x0), dptr(xs), dptr(obs), kind, dptr(z0), dptr(c), float(obj_margin), float(basin_tol),
+                                     dptr(z), dptr(obj), iptr(st), iptr(it), dptr(kkt), dptr(lam_g), dptr(lam_x), iptr(which), iptr(n_ok),
+                                     iptr(n_basins), dptr(z_all), dptr(obj_all), iptr(st_all), iptr(it_all)), self._h)
+        out = dict(z=z, obj=obj, status=st, iters=it, kkt=kkt, which=which, n_ok=n_ok, n_basins=n_basins)
+        if multipliers:
+            out["lam_g"] = lam_g; out["lam_x"] = lam_x
+        if want_all:
+            out.update(z_all=z_all, obj_all=obj_all, status_all=st_all, iters_all=it_all)
+        return out
+
+    def solve_multi_device(self, B, d_x0, d_xs, d_obs, obs_kind, d_z0, d_z, controls=None, obj_margin=1e-9, basin_tol=1e-4, d_obj=None,
+                           d_status=None, d_iters=None, d_kkt=None, d_lam_g=None, d_lam_x=None, d_which=None, d_n_ok=None, d_n_basins=None,
+                           d_z_all=None, d_obj_all=None, d_status_all=None, d_iters_all=None, sync=False):
+        """mpcb_solve_multi_device over raw device pointers (ints / c_void_p / DeviceArray), like solve_device; controls stays a host
+        array [K,2] (None = turn_starts(3)).  Waits for the launch lanes and runs on the handle's own stream, asynchronous unless sync.
+        d_*_all are [B,K,...] over the expanded batch, row b * K + k."""
+        c = self._controls(controls)
+        check(lib().mpcb_solve_multi_device(self._h, int(B), c.shape[0], _devptr(d_x0), _devptr(d_xs), _devptr(d_obs), int(obs_kind), _devptr(d_z0),
+                                            dptr(c), float(obj_margin), float(basin_tol), _devptr(d_z), _devptr(d_obj), _devptr(d_status),
+                                            _devptr(d_iters), _devptr(d_kkt), _devptr(d_lam_g), _devptr(d_lam_x), _devptr(d_which), _devptr(d_n_ok),
+                                            _devptr(d_n_basins), _devptr(d_z_all), _devptr(d_obj_all), _devptr(d_status_all), _devptr(d_iters_all),
+                                            1 if sync else 0), self._h)
 
     # ----- evaluate and certify a point (include/mpcbatch.h, "evaluate and certify any point") -------------------------
     def evaluate(self, x0, xs, obs, z, lam_g=None, lam_x=None, x_ref=None, params=None, want_g=True, want_grad=False):
