@@ -177,7 +177,10 @@ int mpcb_device_count(void);
 
 /* Create a solver for one NLP structure on HIP device `device` (replaces ca.nlpsol(...), kin.py:254).
  * MPCB_RESTO_IN_LAUNCH=0 in the environment at this call: the handle runs every restoration phase in a launch of its own instead of
- * inside the lean launch (same results, for A/B timing). */
+ * inside the lean launch (same results, for A/B timing).  Likewise MPCB_LANE0_OWN_STREAM=0: with more than one
+ * launch lane, lane 0 is the handle's own stream and every lane waits for an event recorded there before it launches; and
+ * MPCB_SKIP_EMPTY_PASS=0: the restoration launch behind a lean launch that restores its own instances is made although it has no
+ * instance to continue (both: the behaviour before DESIGN.md section 5.4's last part, same results, for A/B timing). */
 int mpcb_create(const mpcb_config* cfg, int32_t device, mpcb_handle** out);
 int mpcb_destroy(mpcb_handle* h);
 const char* mpcb_last_error(const mpcb_handle* h);   /* h may be NULL: last creation error */
@@ -222,7 +225,7 @@ int mpcb_solve_device(mpcb_handle* h, int32_t B,
                       double* d_z, double* d_obj, int32_t* d_status, int32_t* d_iters, double* d_kkt,
                       double* d_lam_g, double* d_lam_x, int32_t sync);
 
-/* Launch lanes.  k = 1 (the default): every call is queued on the handle's one stream, in order.  k > 1: the handle owns k - 1
+/* Launch lanes.  k = 1 (the default): every call is queued on the handle's one stream, in order.  k > 1: the handle owns k
  * further streams, and asynchronous mpcb_solve_device calls (sync = 0) go to the lanes in turn, call j on lane j mod k: up to k
  * consecutive solves are in flight together, so the SIMDs that the slowest instances of one launch leave idle are filled by the
  * next launches — inside one handle.  Calls j and j + k share a lane and are ordered; calls closer than k apart may run
@@ -421,7 +424,7 @@ int mpcb_loop_advance_device(mpcb_handle* h, mpcb_loop* L, double* d_x0, const d
  * Refused before anything is launched: z NULL, one multiplier array without the other, grad_lag without multipliers (MPCB_E_INVALID);
  * x_ref on MPCB_MODEL_DYN or together with a set, a time grid (mpcb_set_time_grid), a device group (MPCB_E_UNSUPPORTED).
  * mpcb_evaluate takes host pointers, waits for the lanes and runs on the handle's stream.  mpcb_evaluate_device takes device pointers and
- * is queued on the lane that took the handle's most recent mpcb_solve_device* call, behind it (lane 0 with one lane or before any solve);
+ * is queued on the lane that took the handle's most recent mpcb_solve_device* call, behind it (the handle's stream with one lane or before any solve);
  * it does not advance the rotation of mpcb_set_inflight, so (solve, evaluate) pairs on rotated buffers overlap as the solves alone do. */
 #define MPCB_EVAL_COLS 7
 int mpcb_evaluate(mpcb_handle* h, int32_t B, const mpcb_params* p,

@@ -435,7 +435,8 @@ struct mpcb_loop {
 struct mpcb_handle {
   mpcb_config cfg;
   int device = 0;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;       // the handle's stream
+  hipStream_t first_stream = nullptr; // the stream mpcb_create made: `stream`, except while the lanes are arranged as ensure_lanes says
   std::string err;
   int nx = 4, nz = 0, ng = 0;
   // scratch for the host-pointer entries
@@ -448,15 +449,25 @@ struct mpcb_handle {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // EV_RING pairs, created on first use
   int ev_head = 0, ev_pending = 0;                     // next pair to record into; pairs recorded and not yet harvested
   int launches = 0; double total_ms = 0, last_ms = 0;
-  // Launch lanes (mpcb_set_inflight): lane 0 IS the handle's stream; lanes 1..K-1 own a stream each.  An asynchronous
-  // mpcb_solve_device goes to the next lane(s) in turn, so that consecutive solves of one handle overlap on the GPU (the next
-  // launch fills the SIMDs the tail of the running one leaves idle) without the caller juggling handles.  Every lane has its own
-  // two-pass scratch: hand-over records [B][WK_SIZE] and, when the caller passes no status array, the status column the passes
-  // communicate through.  `done` marks the end of the lane's last launch; join_lanes() makes the handle's stream wait for it.
+  // Launch lanes (mpcb_set_inflight K): an asynchronous mpcb_solve_device goes to the next lane in turn, so that consecutive solves of
+  // one handle overlap on the GPU (the next launch fills the SIMDs the tail of the running one leaves idle) without the caller
+  // juggling handles.  K = 1: the one lane is the handle's stream.  K > 1: every one of the K lanes owns a stream, and the handle's
+  // stream carries no asynchronous solve — only uploads, sampling, collectives, the synchronous entries and their glue kernels.  A
+  // lane then waits for the handle's stream before it launches (ev_fork, lane_follows_handle) only if that stream has unfinished
+  // work; were lane 0 the handle's stream, it would always have (lane 0's latest solve), and every K-th solve would hold the K - 1
+  // after it back until it has finished.
+  // lanes[0] is always the handle's stream (its scratch serves the synchronous entries); asynchronous lane j is lanes[lane_base + j],
+  // lane_base = 1 while K > 1 and 0 otherwise (MPCB_LANE0_OWN_STREAM=0: always 0, lane 0 is the handle's stream again).  While
+  // lane_base = 1 the stream mpcb_create made serves asynchronous lane 0 and `stream` is one created after every lane's (ensure_lanes).
+  // Every lane has its own two-pass scratch: hand-over records [B][WK_SIZE] and, when the caller passes no status array, the status
+  // column the passes communicate through.  `done` marks the end of the last launch of a lane that owns its stream; join_lanes()
+  // makes the handle's stream wait for every such lane.
   struct Lane { hipStream_t stream = nullptr; double* d_work = nullptr; int32_t* d_st_own = nullptr; int work_cap = 0; hipEvent_t done = nullptr; bool busy = false; };
-  std::vector<Lane> lanes;                             // lanes[0].stream == stream
-  int next_lane = 0;
-  int last_solve_lane = 0;                             // the lane that took the most recent mpcb_solve_device* call: mpcb_evaluate_device queues behind it
+  std::vector<Lane> lanes;
+  int lane_base = 0;
+  int inflight() const { return lanes.empty() ? 1 : (int)lanes.size() - lane_base; }       // K of mpcb_set_inflight
+  int next_lane = 0;                                   // asynchronous lane (0..K-1) of the next mpcb_solve_device* call
+  int last_solve_lane = 0;                             // index in `lanes` of the lane that took the most recent mpcb_solve_device* call: mpcb_evaluate_device queues behind it
   hipEvent_t ev_fork = nullptr;                        // "everything queued so far on the handle's stream", awaited by a lane before it launches
   std::vector<std::vector<hipEvent_t>> marks;          // mpcb_event_record: per slot one event per lane stream
   std::vector<double> tgrid_host;                      // host copy of the time grid (handed to the peers of a device group)
@@ -474,6 +485,8 @@ struct mpcb_handle {
   std::vector<mpcb_loop*> loops;                       // live stepwise loops of this handle (freed at mpcb_destroy likewise)
   int loops_created = 0;                               // the next loop's id
   bool resto_in_launch = true;                         // MPCB_RESTO_IN_LAUNCH=0 at mpcb_create: every restoration phase in a launch of its own (A/B runs)
+  bool lane0_own_stream = true;                        // MPCB_LANE0_OWN_STREAM=0 at mpcb_create: asynchronous lane 0 is the handle's stream (A/B runs)
+  bool skip_empty_pass = true;                         // MPCB_SKIP_EMPTY_PASS=0 at mpcb_create: every pass of the plan is launched (A/B runs)
 };
 
 namespace {
@@ -611,33 +624,63 @@ int launch_kernel(mpcb_handle* h, hipStream_t stream, K kernel, const MpcbKArgs&
 }
 
 // the handle's stream waits for every lane that has a launch outstanding: called by everything that may consume the results of,
-// or overwrite the inputs of, asynchronous solves (downloads, uploads, collectives, the closed loop, mpcb_sync ...)
+// or overwrite the inputs of, asynchronous solves (downloads, uploads, collectives, the closed loop, mpcb_sync ...).  (`busy` is only
+// ever set on a lane that owns its stream.)
 int join_lanes(mpcb_handle* h) {
-  for (size_t i = 1; i < h->lanes.size(); ++i) {
-    auto& L = h->lanes[i];
+  for (auto& L : h->lanes) {
     if (L.busy) { HIP_TRY(h, hipStreamWaitEvent(h->stream, L.done, 0)); L.busy = false; }
   }
   return MPCB_OK;
 }
 
+// K = k asynchronous lanes.  The caller has waited for everything in flight (mpcb_set_inflight: mpcb_sync), so no stream is destroyed
+// under outstanding work, in either direction; every lane is made anew (its scratch grows again with the first solve).
+// The runtime gives each new stream the hardware queue that serves the fewest streams, and streams of one queue run their kernels one
+// after the other.  With four queues and sixteen lanes the lanes must therefore sit four to a queue: a 17th stream created BEFORE them
+// shifts them to 3, 4, 4 and 5, and the queue with five sets the pace (profiles/lane_order.txt §2).  So the lanes keep the creation
+// order they had when lane 0 was the handle's stream: the stream mpcb_create made goes to asynchronous lane 0, the others follow, and
+// the handle's own stream is created last.
 int ensure_lanes(mpcb_handle* h, int k) {
-  if (h->lanes.empty()) { h->lanes.resize(1); h->lanes[0].stream = h->stream; }
-  while ((int)h->lanes.size() > k) {
-    auto& L = h->lanes.back();
+  for (auto& L : h->lanes) {
     if (L.d_work) (void)hipFree(L.d_work);
     if (L.d_st_own) (void)hipFree(L.d_st_own);
     if (L.done) (void)hipEventDestroy(L.done);
-    if (L.stream && L.stream != h->stream) (void)hipStreamDestroy(L.stream);
-    h->lanes.pop_back();
+    if (L.stream && L.stream != h->stream && L.stream != h->first_stream) (void)hipStreamDestroy(L.stream);
   }
-  while ((int)h->lanes.size() < k) {
+  h->lanes.clear();
+  if (h->stream != h->first_stream) { (void)hipStreamDestroy(h->stream); h->stream = h->first_stream; }
+  h->lane_base = (k > 1 && h->lane0_own_stream) ? 1 : 0;
+  h->lanes.resize(1);
+  for (int j = h->lane_base ? 0 : 1; j < k; ++j) {     // the lanes that own a stream
     mpcb_handle::Lane L;
-    HIP_TRY(h, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    if (j == 0) L.stream = h->first_stream;
+    else HIP_TRY(h, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
     HIP_TRY(h, hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
     h->lanes.push_back(L);
   }
+  if (h->lane_base) HIP_TRY(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  h->lanes[0].stream = h->stream;
   if (!h->ev_fork) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   h->next_lane = 0; h->last_solve_lane = 0;
+  return MPCB_OK;
+}
+
+// Work queued so far on the handle's stream (uploads, scene sampling, a reset) happens before what lane `lane` is given next.  The
+// runtime is asked whether that stream has anything unfinished; only then does the lane wait for an event recorded there.  (Recording
+// on an idle stream is not free of consequences: the marker goes into the stream's hardware queue behind the kernels of every lane
+// that shares that queue, and the lane would wait for those — profiles/lane_order.txt §2.)
+int lane_follows_handle(mpcb_handle* h, int lane) {
+  if (h->lanes.empty()) { int rc = ensure_lanes(h, 1); if (rc != MPCB_OK) return rc; }
+  const hipStream_t s = h->lanes[lane].stream;
+  if (s == h->stream) return MPCB_OK;
+  if (h->lane0_own_stream) {                           // (MPCB_LANE0_OWN_STREAM=0: the event is recorded and awaited every time, as it was)
+    const hipError_t q = hipStreamQuery(h->stream);
+    if (q == hipSuccess) return MPCB_OK;               // everything queued there has finished already
+    (void)hipGetLastError();                           // hipErrorNotReady is an answer, not an error to find later
+    if (q != hipErrorNotReady) return fail(h, MPCB_E_DEVICE, "hipStreamQuery: %s", hipGetErrorString(q));
+  }
+  HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
+  HIP_TRY(h, hipStreamWaitEvent(s, h->ev_fork, 0));
   return MPCB_OK;
 }
 
@@ -665,13 +708,9 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
     if (need > mpcbd::LDS_MAX_BYTES) return fail(h, MPCB_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", need);
   }
   if (a.B == 0) return MPCB_OK;
-  if (h->lanes.empty()) { int rc = ensure_lanes(h, 1); if (rc != MPCB_OK) return rc; }
+  { int rc = lane_follows_handle(h, lane_id); if (rc != MPCB_OK) return rc; }
   mpcb_handle::Lane& L = h->lanes[lane_id];
   const hipStream_t stream = L.stream;
-  if (lane_id > 0) {                   // work queued earlier on the handle's stream (uploads, scene sampling) happens before this launch
-    HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
-    HIP_TRY(h, hipStreamWaitEvent(stream, h->ev_fork, 0));
-  }
   a.work = nullptr;
   if (mpcbd::multi_pass(h->cfg)) {
     if (a.B > L.work_cap) {       // grows with the largest batch seen (first call of a given size only)
@@ -702,15 +741,18 @@ int launch_solve(mpcb_handle* h, const MpcbKArgs& a_in, int lane_id = 0) {
     a.pass = plan.pass[i];
     const bool resto = a.pass == MPCB_PASS_RESTO;
     // a lean launch that runs the restoration phase of its instances itself gets the restoration layout's LDS; the restoration launch
-    // after it then finds no instance to continue
-    a.resto_here = mpcbd::resto_in_launch(v, h->cfg.N, plan, i, h->resto_in_launch ? -1 : 0) ? 1 : 0;
+    // after it would find no instance to continue, yet each of its workgroups would wait for a whole wave slot behind the other solves
+    // and hold the lane's stream meanwhile: it is not launched
+    const int force = h->resto_in_launch ? -1 : 0;
+    if (h->skip_empty_pass && mpcbd::pass_is_empty(v, h->cfg.N, plan, i, force)) continue;
+    a.resto_here = mpcbd::resto_in_launch(v, h->cfg.N, plan, i, force) ? 1 : 0;
     int rc = mpcbd::visit(v, resto, [&](auto inst) { return launch_kernel(h, stream, kernel_of(inst), a, lds[resto || a.resto_here]); });
     if (rc != MPCB_OK) return rc;
     HIP_TRY(h, hipGetLastError());
   }
   HIP_TRY(h, hipEventRecord(evp.second, stream));
   h->ev_head = (h->ev_head + 1) % mpcb_handle::EV_RING; ++h->ev_pending;
-  if (lane_id > 0) { HIP_TRY(h, hipEventRecord(L.done, stream)); L.busy = true; }
+  if (stream != h->stream) { HIP_TRY(h, hipEventRecord(L.done, stream)); L.busy = true; }
   return MPCB_OK;
 }
 
@@ -775,14 +817,14 @@ int solve_on_device(mpcb_handle* h, const SolveArgs& s, int lane_id = 0) {
   return launch_solve(h, a, lane_id);
 }
 
-// One asynchronous solve on the next lane in turn: call k on lane k mod K (K = 1: the handle's stream).  Up to K consecutive calls
+// One asynchronous solve on the next lane in turn: call k on lane k mod K (K = 1: the handle's stream; K > 1: none of them is).  Up to K consecutive calls
 // are then in flight together, each a full-depth launch that fills the SIMDs the tails of the others leave idle; calls k and k + K
 // share a lane and are ordered.  Measured alternatives (C2, 4096 instances, MI355X): cutting every call into K chunks, chunk c on
 // lane c: 1.11 M solves/s against 1.48 M (only one batch's worth of workgroups is ever queued); cutting a lone synchronous call
 // into chunks: 5.5 ms per call against 4.2 ms for the single launch — so the host-pointer entries stay one launch on lane 0.
 int solve_next_lane(mpcb_handle* h, const SolveArgs& s, int32_t sync) {
-  const int K = h->lanes.empty() ? 1 : (int)h->lanes.size();
-  const int lane = K == 1 ? 0 : h->next_lane;
+  const int K = h->inflight();
+  const int lane = K == 1 ? 0 : h->lane_base + h->next_lane;
   if (K > 1) h->next_lane = (h->next_lane + 1) % K;
   h->last_solve_lane = lane;
   int rc = solve_on_device(h, s, lane);
@@ -923,22 +965,13 @@ int check_loop_use(mpcb_handle* h, const mpcb_loop* L) {
 
 // the lane an asynchronous call of the loop runs on: loop id mod K, K the current mpcb_set_inflight
 int loop_lane(mpcb_handle* h, const mpcb_loop* L) {
-  const int K = h->lanes.empty() ? 1 : (int)h->lanes.size();
-  return L->id % K;
-}
-
-// work queued so far on the handle's stream (uploads, scene sampling, a reset) happens before what a lane is given next
-int lane_follows_handle(mpcb_handle* h, int lane) {
-  if (h->lanes.empty()) { int rc = ensure_lanes(h, 1); if (rc != MPCB_OK) return rc; }
-  if (lane > 0) {
-    HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
-    HIP_TRY(h, hipStreamWaitEvent(h->lanes[lane].stream, h->ev_fork, 0));
-  }
-  return MPCB_OK;
+  const int K = h->inflight();
+  return K == 1 ? 0 : h->lane_base + L->id % K;
 }
 
 int lane_done(mpcb_handle* h, int lane) {
-  if (lane > 0) { auto& Ln = h->lanes[lane]; HIP_TRY(h, hipEventRecord(Ln.done, Ln.stream)); Ln.busy = true; }
+  auto& Ln = h->lanes[lane];
+  if (Ln.stream != h->stream) { HIP_TRY(h, hipEventRecord(Ln.done, Ln.stream)); Ln.busy = true; }
   return MPCB_OK;
 }
 
@@ -1048,13 +1081,17 @@ int mpcb_create(const mpcb_config* cfg, int32_t device, mpcb_handle** out) {
   if (device < 0 || device >= ndev) return fail(nullptr, MPCB_E_INVALID, "device %d outside 0..%d", device, ndev - 1);
   mpcb_handle* h = new mpcb_handle();
   h->cfg = *cfg; h->device = device;
-  { const char* e = std::getenv("MPCB_RESTO_IN_LAUNCH"); h->resto_in_launch = !(e && e[0] == '0' && e[1] == 0); }
+  const auto switched_off = [](const char* name) { const char* e = std::getenv(name); return e && e[0] == '0' && e[1] == 0; };
+  h->resto_in_launch = !switched_off("MPCB_RESTO_IN_LAUNCH");
+  h->lane0_own_stream = !switched_off("MPCB_LANE0_OWN_STREAM");
+  h->skip_empty_pass = !switched_off("MPCB_SKIP_EMPTY_PASS");
   int nx, nz, ng; mpcb_dims(cfg, &nx, &nz, &ng);
   h->nx = nx; h->nz = nz; h->ng = ng;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
     delete h;
     return fail(nullptr, MPCB_E_DEVICE, "cannot create a stream on device %d", device);
   }
+  h->first_stream = h->stream;
   *out = h;
   return MPCB_OK;
 }
@@ -1590,8 +1627,7 @@ int mpcb_evaluate_device(mpcb_handle* h, int32_t B, const mpcb_params* p, const 
   e.cfgs = p ? p->d_cfgs : nullptr;
   HIP_TRY(h, hipSetDevice(h->device));
   // behind the most recent asynchronous solve, on its lane; the rotation of mpcb_set_inflight is not advanced
-  const int K = h->lanes.empty() ? 1 : (int)h->lanes.size();
-  const int lane = h->last_solve_lane < K ? h->last_solve_lane : 0;
+  const int lane = h->last_solve_lane < (int)h->lanes.size() ? h->last_solve_lane : 0;
   { int rc = lane_follows_handle(h, lane); if (rc != MPCB_OK) return rc; }
   { int rc = launch_eval(h, h->lanes[lane].stream, e); if (rc != MPCB_OK) return rc; }
   { int rc = lane_done(h, lane); if (rc != MPCB_OK) return rc; }

@@ -1,5 +1,6 @@
 // mpcb_dispatch.h — which solve instantiation serves a config, how much LDS it gets, whether it fuses its second attempt, in which
-// order the passes of a solve run, and which lean launch runs the restoration phase of its instances itself.  Host only, plain C++17;
+// order the passes of a solve run, which lean launch runs the restoration phase of its instances itself, and which pass is therefore
+// not launched.  Host only, plain C++17;
 // included behind the kernel headers by mpcb_api.hip (which launches what this header selects) and by tests/emu/wave_emu.cpp and
 // tests/emu_resto/resto_emu.cpp (which step the same selection on the CPU).  The policy is stated here and nowhere else.
 #pragma once
@@ -110,7 +111,8 @@ inline Plan pass_plan(const mpcb_config& c, bool start_given, bool fused) {
 // when the slowest instance of the lean launch has finished, and it holds its stream for the length of its own slowest instance.  Where
 // this rule says yes, the wave of the lean launch that ends with MPCB_ST_NEEDS_RESTO calls the restoration instantiation itself, at once
 // and on the same LDS; that instantiation reads z, the status and the hand-over record back from memory exactly as in a launch of its
-// own, so the results are the same by construction.  The MPCB_PASS_RESTO launch of the plan stays and finds no instance to continue.
+// own, so the results are the same by construction.  The MPCB_PASS_RESTO pass stays in the plan, has no instance left to continue, and
+// is not launched (pass_is_empty below).
 // Only the Euler kin<0|1> kernels without GEN (plain, tracking, per-instance) do this: their restoration twins need no scratch, those of
 // kin<3> and dyn<1|3> spill 230-600 B and would take the lean kernels' zero scratch with them.  -DMPCB_NO_RESTO_IN_LAUNCH: no
 // instantiation does (A/B builds).  The kernels' `if constexpr` (mpcb_api.hip) and the host's launch both read restores_here().
@@ -134,6 +136,14 @@ inline bool resto_in_launch(const Variant& v, int N, const Plan& plan, int i, in
   if (force == 0 || !restores_here(v)) return false;
   if (plan.pass[i] == MPCB_PASS_RESTO || i + 1 >= plan.n || plan.pass[i + 1] != MPCB_PASS_RESTO) return false;
   return force == 1 || wgs_per_cu(lds_bytes(v, N, true)) >= wgs_per_cu(lds_bytes(v, N, false));
+}
+
+// Is pass i of the plan known to have no work before anything runs?  Exactly when it is the restoration pass and the pass before it
+// restores in its own launch: that launch leaves no instance at MPCB_ST_NEEDS_RESTO, so every workgroup of pass i would return at once,
+// yet as a launch each of them waits for a whole wave slot (the restoration kernel's registers and LDS) behind the other solves in
+// flight, and the stream is held meanwhile.  The launcher skips such a pass; pass_plan and Plan describe the solve, not the launches.
+inline bool pass_is_empty(const Variant& v, int N, const Plan& plan, int i, int force = -1) {
+  return i > 0 && plan.pass[i] == MPCB_PASS_RESTO && resto_in_launch(v, N, plan, i - 1, force);
 }
 
 // ---- run-time variant -> compile-time template arguments ------------------------------------------------------------------------------

@@ -29,6 +29,14 @@ for g in "abcde":
     rows = list(csv.DictReader(open(files[0])))
     rows = [r for r in rows if "mpcb_kernel" in r["Kernel_Name"]]
     all_ids = sorted(set(int(r["Dispatch_Id"]) for r in rows))
+    # the launches of one solve are read from the dispatches themselves: the library does not launch a restoration pass that is known to
+    # be empty (mpcbd::pass_is_empty), so bench.py's kernel_launches_per_solve (the passes of the plan) can exceed them.  Every solve of
+    # the run launches the same kernels in the same order; the shortest period of the kernel-name sequence is one solve.
+    names = [next(r["Kernel_Name"] for r in rows if int(r["Dispatch_Id"]) == d) for d in all_ids]
+    period = next((p for p in range(1, len(names) + 1) if len(names) % p == 0 and names == names[:p] * (len(names) // p)), 0)
+    if period and period != n_launch:
+        lines.append("# %d launches per solve in the dispatches (the plan has %d passes)" % (period, n_launch))
+    n_launch = period or n_launch
     if len(all_ids) % n_launch:
         lines.append("# WARNING: %d solve-kernel dispatches are not a multiple of %d launches per solve" % (len(all_ids), n_launch))
     ids = all_ids[-n_launch:]
